@@ -21,7 +21,19 @@ host/tkmk_service.hpp, C++ over the C ABI of libtkmk_hip.so).  Nothing inside th
               BASELINE.json configs[4]'s shape as a secondary: a point-sharded MSM with one RCCL all_gather of the 144-byte partial results.
 value = constraint slots proved per second by the whole job = 2^22 * N * steps / max-over-ranks elapsed.
 
-roofline (same JSON line): the dominant kernel of a proof, k_accumulate_chunks (bucket accumulation of every MSM).  Its launch
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) stages the files, opens the prover, warms up, times the K steps and prints
+the line: headline figures and what the timed steps' own counters give (per_proof_s, work_per_proof, ...).  Everything that takes
+runs of its own — the serialised profiling pass with the roofline and per-kernel figures, the CPU baseline, the secondary
+objects — runs only with --full (--no-serial-pass / --no-cpu-baseline / --no-secondary then drop single parts of it).
+--dump-outputs DIR writes the proof of the last timed step (proof.json, the caller's result) as DIR/proof_<name>.npy, float64
+16-bit limbs, little-endian: a G1 point is (2, 24) = x, y; a scalar is (16,).  The production library draws its blinding scalars
+from getrandom, so its proofs differ from run to run by design; with --dump-outputs every proof of the run (warm-up and timed)
+goes through the testing-mode build of the same library (libtkmk_prover_testing.so: the same commitments and rounds, the degree
+bounds measured and checked as well) with blinding scalars fixed by SEED, so that the same arguments give the same proof bytes.
+Those measurements make a dump run's steps about 5 % slower (configs[3]: 217 ms against 205-208 ms per proof); the headline is a
+plain run's.
+
+roofline (same JSON line, --full): the dominant kernel of a proof, k_accumulate_chunks (bucket accumulation of every MSM).  Its launch
 duration is measured live with HIP events recorded on the launch stream (tkmk_profile_*: recorded without synchronising) in a
 SERIALISED PROFILING PASS run right after the timed region: the same proofs with the multi-MSM pipeline narrowed to one internal
 stream (tkmk_msm_set_pipeline_streams(1)), so that no two kernels of a commit batch overlap and a section's time is the kernel's own
@@ -31,11 +43,11 @@ behind the other streams' kernels, so those figures are kept apart and labelled 
 committed point (scalar + base read once) / launch time, against 8 TB/s; `traffic` from the committed
 rocprofv3 PMC summary (profiles/traffic.json).  The kernel is integer-VALU bound by construction; valu_roofline gives the
 fraction of the measured v_mad_u64_u32 rate.
-cpu_baseline: the oracle (a C port — the reference's Rust + ICICLE CPU prover cannot be built offline) on a bounded sample: one
+cpu_baseline (--full): the oracle (a C port — the reference's Rust + ICICLE CPU prover cannot be built offline) on a bounded sample: one
 2^20-point MSM and one 1024 x 1024 bivariate NTT on the box's host cores, checked against the GPU, scaled by the proof's counted
 MSM points / NTT elements: a LOWER bound on CPU prove time (polynomial bookkeeping and host glue come on top), labelled as such.
 
-Secondary objects (N = 1; each records {"error": ...} instead of costing the line if it fails):
+Secondary objects (--full, N = 1; each records {"error": ...} instead of costing the line if it fails):
   production_2p20  the reference's production shape (s_max = 256, 166 placements; published walls 45.70 s CPU / 21.08 s CUDA)
   bin_prove_cold   the one-shot binary, process start -> proof.json (device init, CRS load, proof: what prove/src/main.rs:28-84 times
                    and the reference's published walls include), configs[3] from .tkcrs; production shape from .tkcrs and from .rkyv
@@ -116,8 +128,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--s-max", type=int, default=1024, help="1024 = BASELINE.json configs[3] (2^22 constraint slots); 256 = the reference's production shape")
     ap.add_argument("--placements", type=int, default=None, help="used placements (default: all s_max)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip production_2p20 / msm_2p24 / ntt / msm_2p28_one_gpu")
+    ap.add_argument("--full", action="store_true", help="also everything that takes runs of its own: the serialised profiling pass (roofline, "
+                    "per-kernel figures), the CPU baseline and the secondary objects; a plain run times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's proof as DIR/proof_<name>.npy (float64 "
+                    "16-bit limbs); the run's proofs then use fixed blinding scalars (testing-mode library) so that they repeat")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip production_2p20 / msm_2p24 / ntt / msm_2p28_one_gpu")
     ap.add_argument("--one-proof", action="store_true", help="N > 1: the N GPUs prove ONE circuit together (tkmk_prover_open_sharded: commit tables and "
                     "commitments sharded by grid row, one all-gather per round) instead of N independent proofs; value = 2^22 / time per proof, scaling strong")
     ap.add_argument("--msm-sharded", action="store_true", help="N > 1: also time the point-sharded MSM of BASELINE.json configs[4] (2^25 points per rank)")
@@ -128,10 +144,12 @@ def main():
     ap.add_argument("--ntt-sharded-logn", type=int, default=20, help="length of one NTT of the batch leg (2^20 = configs[2])")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL over xGMI; default) or gloo (rehearsal of the N>1 path)")
     ap.add_argument("--share-gpu0", action="store_true", help="rehearsal only: every rank uses GPU 0 (needs --dist-backend gloo)")
-    ap.add_argument("--no-serial-pass", action="store_true", help="skip the serialised profiling pass (for a rocprofv3 run whose kernel "
+    ap.add_argument("--no-serial-pass", action="store_true", help="with --full: skip the serialised profiling pass (for a rocprofv3 run whose kernel "
                     "statistics should hold the timed region's launches only); the roofline then carries the queue-inclusive event times")
     ap.add_argument("--workdir", default=None, help="where the staged files go (default: a fresh temporary directory)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -139,13 +157,18 @@ def main():
     if world != args.gpus:
         raise SystemExit("--gpus %d but WORLD_SIZE=%d (launch with torch.distributed.run --nproc-per-node N)" % (args.gpus, world))
 
-    import torch
     import tkmk
     from tkmk import service
-    if not torch.cuda.is_available():
+    torch = None
+    if world > 1:           # torch.distributed carries the ranks' barriers and maxima; one GPU needs no torch (its first import is slow)
+        import torch
+        if not torch.cuda.is_available():
+            raise SystemExit("bench.py needs a GPU: the product has no CPU fallback")
+    if tkmk.device_count() < 1:
         raise SystemExit("bench.py needs a GPU: the product has no CPU fallback")
     dev = 0 if args.share_gpu0 else local_rank
-    torch.cuda.set_device(dev)
+    if torch is not None:
+        torch.cuda.set_device(dev)
     tkmk.set_device(dev)
     dist = None
     if world > 1:
@@ -163,7 +186,7 @@ def main():
     def barrier():
         if dist is not None:
             dist.barrier()
-        torch.cuda.synchronize()
+            torch.cuda.synchronize()
         tkmk.synchronize()
 
     # --- stage the files every rank reads (untimed): rank 0 generates the circuit, its witness and the CRS ---
@@ -194,17 +217,20 @@ def main():
             comm_report = {"size_reported_by_communicator": dist_size(shard_comm), "ranks": lines,
                            "distinct_devices": len({(l["pci_bus_id"], l["uuid"]) for l in lines}),
                            "gathered_with": "tkmk_comm_all_gather_host over this communicator"}
-        prover = service.Prover(files["qap"], files["crs"], comm=shard_comm if one_proof else None)      # circuit-static state -> HBM, once (sharded: 1/N of the tables)
+        # --dump-outputs: the testing-mode build with blinding scalars fixed by SEED (the production build draws them from getrandom)
+        fixed_blinding = args.dump_outputs is not None
+        prover = service.Prover(files["qap"], files["crs"], testing=fixed_blinding, comm=shard_comm if one_proof else None)      # circuit-static state -> HBM, once (sharded: 1/N of the tables)
         open_s = time.perf_counter() - t
         jobs_in_flight = 1 if one_proof else world                                # proofs a step completes
         out_dir = os.path.join(files["tmp"], "out_rank%d" % rank)
+        mixer_json = _write_fixed_mixer(os.path.join(files["tmp"], "mixer_rank%d.json" % rank)) if fixed_blinding else None
 
         def step():
-            return prover.prove(files["synth"], out_dir, want_json=False)[1]
+            return prover.prove(files["synth"], out_dir, testing_mixer_json=mixer_json, want_json=False)[1]
 
         for _ in range(args.warmup):
             step()
-        tkmk.profile_enable(True)
+        tkmk.profile_enable(args.full)          # HIP events in the timed region feed --full's queue-inclusive figures only
         tkmk.profile_reset()
         tkmk.native_stats_reset()
         barrier()
@@ -218,10 +244,12 @@ def main():
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             elapsed = float(tt.item())
         stats = tkmk.native_stats()
+        if args.dump_outputs is not None and rank == 0:      # proof.json of the last timed step, before any later proof overwrites it
+            _dump_proof(os.path.join(out_dir, "proof.json"), args.dump_outputs)
         q_sections, q_ntt_ms, (q_acc_ms, q_acc_cnt) = _read_sections(tkmk, args.steps)      # queue-inclusive: three streams in flight
-        # ---- serialised profiling pass (untimed for the headline): the same proofs, one internal stream, every kernel alone ----
+        # ---- serialised profiling pass (--full; untimed for the headline): the same proofs, one internal stream, every kernel alone ----
         streams_default = tkmk.msm_get_pipeline_streams()
-        serial = not args.no_serial_pass and streams_default > 1
+        serial = args.full and not args.no_serial_pass and streams_default > 1
         if serial:
             ser_proofs = max(1, min(args.steps, 3))
             tkmk.msm_set_pipeline_streams(1)
@@ -281,7 +309,8 @@ def main():
                                        "table, the Lagrange-basis tables derived from it, the subcircuit library; the proof bytes are those of the reference's "
                                        "algorithm (DESIGN.md section 4 lists the algebraically equal forms used)",
                            "constraint_slots_per_proof": slots, "r1cs_rows_per_proof": files["r1cs_rows"], "proofs_per_step": jobs_in_flight,
-                           "host_side": "native C++ (libtkmk_prover.so over the C ABI of libtkmk_hip.so)",
+                           "host_side": "native C++ (%s over the C ABI of libtkmk_hip.so)" % os.path.basename(service.TESTING_LIB_PATH if fixed_blinding else service.LIB_PATH),
+                           "blinding": "fixed by SEED (--dump-outputs)" if fixed_blinding else "fresh from getrandom every proof",
                            "sharding": ("ONE proof over %d GPUs (tkmk_prover_open_sharded): commit tables, transforms, streaming passes and the witness "
                                         "side divided by columns r mod N; one all-to-all per transform, one all-gather per commit batch; transcript replicated" % world) if one_proof
                            else "independent proofs per GPU" if world > 1 else "none"},
@@ -294,18 +323,19 @@ def main():
                 "work_per_proof": {"msm_points": points_per_proof, "msm_calls": stats["msm.calls"] / args.steps,
                                    "ntt_elements": stats["ntt.elements"] / args.steps, "ntt_calls": stats["ntt.calls"] / args.steps,
                                    "algorithmic_bytes": ALG_BYTES_PER_POINT * points_per_proof + ALG_BYTES_PER_NTT_ELEMENT * stats["ntt.elements"] / args.steps},
+            }
+            if args.full:
                 # kernel times of one proof, each kernel running alone (serialised pass: one internal stream); their sum is below that
                 # pass's own step time (the rest is polynomial passes that are not bracketed, host phases and launch gaps)
-                "kernel_ms_per_proof": dict(sections, ntt_passes=round(ntt_ms, 3)),
-                "serialised_pass": {"ran": serial, "pipeline_streams": 1 if serial else streams_default, "proofs": ser_proofs, "ms_per_step": ser_elapsed / ser_proofs * 1e3,
-                                    "bracketed_kernels_ms_per_proof": round(sum(v["ms_per_proof"] for v in sections.values()) + ntt_ms, 3),
-                                    "note": "untimed for the headline; same proofs with tkmk_msm_set_pipeline_streams(1): section times are "
-                                            "kernel durations as rocprofv3 reports them (profiles/r04_prove_configs3_kernel_stats_1stream.csv)"},
-                "kernel_ms_per_proof_queue_inclusive": dict(q_sections, ntt_passes=round(q_ntt_ms, 3), pipeline_streams=streams_default,
-                                                            note="HIP events in the timed region: with several streams in flight an event pair "
-                                                                 "also brackets the wait behind the other streams' kernels; NOT kernel time"),
-            }
-            if acc_cnt:
+                out["kernel_ms_per_proof"] = dict(sections, ntt_passes=round(ntt_ms, 3))
+                out["serialised_pass"] = {"ran": serial, "pipeline_streams": 1 if serial else streams_default, "proofs": ser_proofs, "ms_per_step": ser_elapsed / ser_proofs * 1e3,
+                                          "bracketed_kernels_ms_per_proof": round(sum(v["ms_per_proof"] for v in sections.values()) + ntt_ms, 3),
+                                          "note": "untimed for the headline; same proofs with tkmk_msm_set_pipeline_streams(1): section times are "
+                                                  "kernel durations as rocprofv3 reports them (profiles/r04_prove_configs3_kernel_stats_1stream.csv)"}
+                out["kernel_ms_per_proof_queue_inclusive"] = dict(q_sections, ntt_passes=round(q_ntt_ms, 3), pipeline_streams=streams_default,
+                                                                  note="HIP events in the timed region: with several streams in flight an event pair "
+                                                                       "also brackets the wait behind the other streams' kernels; NOT kernel time")
+            if args.full and acc_cnt:
                 avg_ms = acc_ms / acc_cnt
                 alg = ALG_BYTES_PER_POINT * ser_stats["msm.points"] / acc_cnt      # per launch: one launch per MSM
                 achieved = alg / (avg_ms * 1e-3) / 1e9
@@ -341,9 +371,9 @@ def main():
                     out[key] = {"error": "%s: %s" % (type(e).__name__, e)}
 
             tkmk.release_scratch()
-            if world == 1 and not args.no_cpu_baseline:
+            if args.full and world == 1 and not args.no_cpu_baseline:
                 leg("cpu_baseline", lambda: _cpu_baseline(tkmk, out["work_per_proof"], slots, elapsed / args.steps))
-            if world == 1 and not args.no_secondary:
+            if args.full and world == 1 and not args.no_secondary:
                 leg("bin_prove_cold", lambda: _cold_leg(prove_bench, files, args.s_max))
                 leg("production_2p20", lambda: _production_leg(prove_bench))
                 tkmk.release_scratch()
@@ -360,6 +390,31 @@ def main():
             shutil.rmtree(files["tmp"], ignore_errors=True)
     if dist is not None:
         dist.destroy_process_group()
+
+
+def _write_fixed_mixer(path):
+    """blinding scalars drawn from random.Random(SEED), in the JSON form of the testing-mode hook (host/tkmk_prover.hpp mixer_from_json)"""
+    import random
+    from tkmk.prove import random_mixer
+    hx = lambda v: [hx(e) for e in v] if isinstance(v, list) else "0x%x" % v          # noqa: E731
+    with open(path, "w") as f:
+        json.dump({k: hx(v) for k, v in random_mixer(random.Random(SEED)).items()}, f)
+    return path
+
+
+def _dump_proof(proof_json, out_dir):
+    """proof.json -> out_dir/proof_<name>.npy: each coordinate or scalar as little-endian 16-bit limbs in float64 (exact); a G1 point
+    (2, 24) = x, y (Fq, 381 bits), a scalar (16,) (Fr, 255 bits); names and order of tkmk/proofio.py"""
+    from tkmk import proofio
+    with open(proof_json) as f:
+        points, scalars = proofio.recover_proof(json.load(f))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, p in points.items():
+        limbs = np.frombuffer(bytes(p), "<u2").reshape(2, 24)
+        np.save(os.path.join(out_dir, "proof_%s.npy" % name), limbs.astype(np.float64))
+    for name, v in scalars.items():
+        limbs = np.frombuffer(int(v).to_bytes(32, "little"), "<u2")
+        np.save(os.path.join(out_dir, "proof_%s.npy" % name), limbs.astype(np.float64))
 
 
 def _traffic_from_profiles(key):

@@ -12,7 +12,7 @@ R=$PWD
 OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="--no-secondary --no-cpu-baseline"
+B="--full --no-secondary --no-cpu-baseline"     # --full: the serialised pass and the roofline, without the other legs
 export TKMK_MSM_STREAMS=1
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats1 -- python3 $R/bench.py $B --steps 3 --warmup 1 "$@" > $OUT/bench_stats_1stream.json 2> $OUT/stats1.err
 unset TKMK_MSM_STREAMS
