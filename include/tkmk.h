@@ -213,6 +213,12 @@ tkmk_error tkmk_msm_multi(const tkmk_msm_job *jobs, int n_jobs, const tkmk_msm_c
 #define TKMK_BASES_PLAIN 0
 #define TKMK_BASES_MONTGOMERY 1
 #define TKMK_BASES_CONVERTED 2
+/* TKMK_BASES_ACC_READY (tkmk_msm_multi_ex and its sharded twin only) is decided PER JOB: a job with table_c > 0 takes `bases` as a
+ * table made by bls12_381_msm_precompute_bases_acc (128-byte rows, 128-byte aligned: a pointer that is not is refused with
+ * TKMK_ERR_INVALID_ARGUMENT, and so are a table job of a single point and one with table_factor < 2: there is no one-level table job in
+ * this form); a job with table_c == 0, with or without base_index, is taken
+ * exactly as under TKMK_BASES_CONVERTED (96-byte records).  Results are bit-identical to TKMK_BASES_CONVERTED over the 96-byte table. */
+#define TKMK_BASES_ACC_READY 3
 typedef struct {
     const tkmk_fr *scalars;
     const tkmk_g1_affine *bases;
@@ -226,7 +232,8 @@ typedef struct {
      * [j * base_table_len, (j + 1) * base_table_len)) holds the 2^(table_c * W' * j) multiples of level 0, W' = ceil(windows /
      * table_factor).  The MSM then runs W' windows of table_c bits over msm_size * table_factor entries — with table_factor =
      * windows a SINGLE bucket set, so that wide windows (table_c up to 20: 13 instead of 16 bucket additions per point) do not
-     * multiply the bucket-reduction work.  Views address level 0; bases_form must be TKMK_BASES_CONVERTED.  Results are
+     * multiply the bucket-reduction work.  Views address level 0; bases_form must be TKMK_BASES_CONVERTED, or TKMK_BASES_ACC_READY
+     * for a table made by bls12_381_msm_precompute_bases_acc.  Results are
      * bit-identical to the plain MSM.  A job with table_c > 16 needs msm_size * table_factor >= 2^18. */
     uint32_t table_c, table_factor;
 } tkmk_msm_job_ex;
@@ -236,6 +243,13 @@ tkmk_error tkmk_msm_multi_ex(const tkmk_msm_job_ex *jobs, int n_jobs, const tkmk
  * the library's resident form for TKMK_BASES_CONVERTED, written to `out` (host or device per cfg->are_results_on_device;
  * out == bases is allowed).  Only meaningful as the `bases` of a later tkmk_msm_multi_ex call. */
 tkmk_error bls12_381_msm_convert_bases(const tkmk_g1_affine *bases, uint64_t n, const tkmk_msm_config *cfg, tkmk_g1_affine *out);
+/* The table of bls12_381_msm_precompute_bases (same levels, same cfg->c / precompute_factor / bitsize semantics) as ACCUMULATE-READY rows
+ * for the table jobs of TKMK_BASES_ACC_READY: n * F' records of 128 bytes, row r at out + 128 r, each on its own 128-byte line (the packed coordinates
+ * of the converted record with infinity marked in band, padded), so that a gather reads one line instead of a record that straddles two.  The record is opaque: only
+ * tkmk_msm_multi_ex reads it, and only a context that sizes its own tables should hold one (the table is 128 / 96 the size of the 96-byte
+ * one).  *out_bytes (if not NULL) receives the size; out == NULL only reports it.  `out` is DEVICE memory on a 128-byte boundary
+ * (TKMK_ERR_INVALID_ARGUMENT otherwise), whatever cfg->are_results_on_device says; `bases` follows cfg->are_points_on_device. */
+tkmk_error bls12_381_msm_precompute_bases_acc(const tkmk_g1_affine *bases, uint64_t n, const tkmk_msm_config *cfg, void *out, uint64_t *out_bytes);
 
 /* ---------------------------------------------------------------------------------------------
  * NTT — replaces icicle_core::ntt::{ntt, initialize_domain, release_domain, get_root_of_unity}

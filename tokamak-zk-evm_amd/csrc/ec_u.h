@@ -12,7 +12,18 @@
 //   X3 = R^2 - (PPP + 2Q)  (sub<4>, t < 3.09)    < 5.03      (invariant restored)
 //   Y3 = [R (Q - X3) + (2p - Y1) PPP] / R'       < 1.03      (sub<8>, sub<2>; ONE reduction for both products)
 //   ZZ3 = ZZ1 PP, ZZZ3 = ZZZ1 PPP                < 1.03
+// add_mixed_signed (the base enters as +Q or -Q, decided by a mask, no negated copy of y is made): only R changes,
+//   R  = +-S2 - Y1  (sub2_signed)   + : S2 + (2p - Y1)        in (0.97, 3.03)
+//                                   - : (2p - S2) + (2p - Y1) in (1.94, 4.00]      so R in (0.97, 4.03) whatever the sign
+//   R enters R^2 and R (Q - X3) only, as an operand of a product: 4.03 p is far below the 2^10 p operand bound and its top limb
+//   (<= 4.03 * 13) far below 2^29; both products return < 1.03 p, so X3 = R^2 - t (sub<4>, t < 3.09) < 5.03 and Y3 < 1.03 as before:
+//   the accumulator invariant and the K of every sub<K> downstream are those of add_mixed.
+//   (2p - Y1) is used once, as the operand c of mul_add against the strict PPP: it is taken WITHOUT its carry sweep (neg2_unswept: limbs
+//   SUB2[i] - Y1[i] < 2^30, top limb <= 25).  A column of mul_add then holds L products < 2^58 (a b), L < 2^59 (c d) and L < 2^58
+//   (m p): 14 * 2^59 + 2 * 14 * 2^58 = 56 * 2^58 < 2^64, checked by FFU_ASSERT on the host; the value is still 2p - Y1 < 2p.
 #pragma once
+#include <type_traits>
+
 #include "ec.h"
 #include "ffu.h"
 
@@ -64,6 +75,45 @@ struct ecu {
         }
         r.y = t;
         return r;
+    }
+    // q or -q by mask (m = 0 or all ones): the borrow sweep of neg() with its result merged by and / or, no select and no branch
+    static FF_HD A neg_masked(const A &q, uint32_t m) {
+        A n = neg(q), r;
+        r.x = q.x;
+#pragma unroll
+        for (int i = 0; i < FU::L; i++) r.y.l[i] = (q.y.l[i] & ~m) | (n.y.l[i] & m);
+        return r;
+    }
+
+    // ---- accumulate-ready table rows (TKMK_BASES_ACC_READY): one 128-byte record on a 128-byte boundary per table row, so that a
+    // gathered row is ONE cache line instead of a 96-byte record that straddles two.  The packed {x R', y R'} words of the converted
+    // record (words [0, N) and [N, 2N)), the rest zero.  Infinity is marked in band: word N - 1 (the top word of x, below 2^30 for any
+    // canonical x of the fields served here) is all ones — one compare in the loop instead of the OR over 2N words.
+    // (Measured against rows of pre-unpacked strict limbs, which lose: tools/experiments/r05_acc_row_unpacked_limbs.patch.)
+    struct alignas(128) Row {
+        uint32_t w[32];
+    };
+    static_assert(2 * FS::N <= 32, "row does not fit its line");
+    static constexpr uint32_t ROW_INF = 0xffffffffu;
+    static FF_HD Row to_row(const affine_t<FS> &rec) {
+        Row r;
+#pragma unroll
+        for (int i = 0; i < 32; i++) r.w[i] = 0;
+#pragma unroll
+        for (int i = 0; i < FS::N; i++) r.w[i] = rec.x.l[i], r.w[FS::N + i] = rec.y.l[i];
+        if (FS::is_zero(rec.x) && FS::is_zero(rec.y)) r.w[FS::N - 1] = ROW_INF;
+        return r;
+    }
+    // what a table kernel stores for the converted record `a`, by the type of its output
+    static FF_HD void to_record(affine_t<FS> &r, const affine_t<FS> &a) { r = a; }
+    static FF_HD void to_record(Row &r, const affine_t<FS> &a) { r = to_row(a); }
+    static FF_HD bool load_row(A &q, const Row &r) {
+        typename FS::E x, y;
+#pragma unroll
+        for (int i = 0; i < FS::N; i++) x.l[i] = r.w[i], y.l[i] = r.w[FS::N + i];
+        q.x = FU::from_packed(x);
+        q.y = FU::from_packed(y);
+        return r.w[FS::N - 1] != ROW_INF;
     }
     static FF_HD X from_affine(const A &q) {
         X r;
@@ -205,6 +255,31 @@ struct ecu {
         r.x = FU::template sub<4>(FU::sqr(rd), t);
         E d = FU::template sub<8>(qq, r.x);
         r.y = FU::mul_add(rd, d, FU::template sub<2>(FU::zero(), p.y), ppp);  // R (Q - X3) + (2p - Y1) PPP, one reduction
+        r.zz = FU::mul(p.zz, pp);
+        r.zzz = FU::mul(p.zzz, ppp);
+        return r;
+    }
+    // p + q or p - q (negate), q an affine point (not infinity): add_mixed with the sign folded into the one subtraction that y enters
+    // (see the bounds at the top); the rare cases that need a negated copy of q make it there
+    static FF_HD X add_mixed_signed(const X &p, const A &q, bool negate) { return add_mixed_masked(p, q, 0u - (uint32_t)negate); }
+    // the same with the sign as a mask (0 or all ones).  The accumulate kernel makes it from the sorted record by an arithmetic shift: a
+    // mask made from a bool is folded back into selects by the compiler (14 v_cndmask_b32 in sub2_signed, seen in the ISA).
+    static FF_HD X add_mixed_masked(const X &p, const A &q, uint32_t m) {
+        if (p.inf) return from_affine(neg_masked(q, m));
+        E u2 = FU::mul(q.x, p.zz);
+        E s2 = FU::mul(q.y, p.zzz);
+        E pd = FU::template sub<8>(u2, p.x);
+        if (FU::maybe_multiple_of_p(pd, 9)) return add_mixed_slow(p, neg_masked(q, m));
+        E rd = FU::sub2_signed(s2, p.y, m);
+        E pp = FU::sqr(pd);
+        E ppp = FU::mul(pd, pp);
+        E qq = FU::mul(p.x, pp);
+        X r;
+        r.inf = false;
+        E t = FU::add_dbl(ppp, qq);
+        r.x = FU::template sub<4>(FU::sqr(rd), t);
+        E d = FU::template sub<8>(qq, r.x);
+        r.y = FU::template mul_add<true>(rd, d, FU::neg2_unswept(p.y), ppp);
         r.zz = FU::mul(p.zz, pp);
         r.zzz = FU::mul(p.zzz, ppp);
         return r;

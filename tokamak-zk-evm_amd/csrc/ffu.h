@@ -97,6 +97,30 @@ struct ffu {
         }
         return norm(t);
     }
+    // 2p - b without the carry sweep: limbs below 2^30 (an operand c of mul_add only)
+    static FF_HD E neg2_unswept(const E &b) {
+        FFU_ASSERT(strict(b) && below(b, 2));
+        E t;
+#pragma unroll
+        for (int i = 0; i < L; i++) t.l[i] = P::SUB2[i] - b.l[i];
+        return t;
+    }
+    // (m ? -a : a) - b + (m ? 4 : 2) p, m = 0 or all ones: the R = S2 - Y1 of a mixed addition whose base enters negated, in the ONE
+    // carry sweep sub<2> does anyway.  -a is (2p - a) limb by limb against the dominating form of 2p; the condition is mask arithmetic
+    // ((a ^ m) + ((C + 1) & m) = C - a when m is all ones, a when m is 0), not a select.  a and b strict, both below 2p; a limb of the
+    // sum is below 2 * 2^30 before the sweep; the result is strict, in (0.97, 3.03) p for m = 0 and (1.94, 4] p for m = ~0 when a, b < 1.03 p.
+    static FF_HD E sub2_signed(const E &a, const E &b, uint32_t m) {
+        FFU_ASSERT(m == 0u || m == ~0u);
+        FFU_ASSERT(strict(a) && strict(b) && below(b, 2) && below(a, 2));
+        E t;
+#pragma unroll
+        for (int i = 0; i < L; i++) {
+            const uint32_t c = P::SUB2[i];
+            FFU_ASSERT(c >= b.l[i] && c >= a.l[i]);
+            t.l[i] = ((a.l[i] ^ m) + ((c + 1u) & m)) + (c - b.l[i]);
+        }
+        return norm(t);
+    }
 
     // Montgomery product a*b/2^(W L) mod p (redundant): strict operands, a*b < 2^20 p^2; strict result < 1.03 p.
     // Product scanning; a 64-bit column accumulator cannot overflow: 2L products < 2^58 plus a carry < 2^35.
@@ -131,10 +155,18 @@ struct ffu {
     // (a*b + c*d)/2^(W L) mod p with ONE Montgomery reduction (the reduction is a third of a product's multiply-adds):
     // strict operands with top limbs <= MASK, a*b + c*d < 2^20 p^2; strict result < 1.03 p.  A column holds up to 3L
     // products < 2^(2W): 42 * 2^58 (W = 29, L = 14) and 30 * 2^56 (W = 28, L = 10) are both below 2^64.
+    // C_UNSWEPT: c is a neg2_unswept() value — limbs below 2^(W+1) instead of strict; its products are below 2^(2W+1), so a column
+    // holds at most L * 2^(2W) + L * 2^(2W+1) + L * 2^(2W) = 4L products' worth of 2^(2W) (56 * 2^58, 40 * 2^56: below 2^64).
+    template <bool C_UNSWEPT = false>
     static FF_HD E mul_add(const E &a, const E &b, const E &c, const E &d) {
-        static_assert(3 * L < (1 << (64 - 2 * (int)W)), "column accumulator would overflow");
-        FFU_ASSERT(strict(a) && strict(b) && strict(c) && strict(d));
-        FFU_ASSERT(a.l[L - 1] <= MASK && b.l[L - 1] <= MASK && c.l[L - 1] <= MASK && d.l[L - 1] <= MASK);
+        static_assert((C_UNSWEPT ? 4 : 3) * L < (1 << (64 - 2 * (int)W)), "column accumulator would overflow");
+        FFU_ASSERT(strict(a) && strict(b) && strict(d));
+        FFU_ASSERT(a.l[L - 1] <= MASK && b.l[L - 1] <= MASK && d.l[L - 1] <= MASK);
+        if (C_UNSWEPT) {
+            for (int i = 0; i < L; i++) FFU_ASSERT(c.l[i] < (1u << (W + 1)));
+        } else {
+            FFU_ASSERT(strict(c) && c.l[L - 1] <= MASK);
+        }
         uint32_t m[L];
         uint64_t acc = 0;
         E r;

@@ -48,6 +48,14 @@ using abi_job = TK_MSM_ABI_JOB;
 using abi_job_ex = TK_MSM_ABI_JOB_EX;
 #endif
 constexpr size_t AFF_BYTES = sizeof(g1_affine_t), FR_BYTES = sizeof(fr_t);
+#ifdef TK_MSM_SYM_PRECOMPUTE_ACC
+// row of a TKMK_BASES_ACC_READY table (ec_u.h)
+using acc_row_t = G1U::Row;
+constexpr size_t ACC_ROW_BYTES = sizeof(acc_row_t);
+static_assert(ACC_ROW_BYTES == 128 && alignof(acc_row_t) == 128, "one row per 128-byte line");
+#else
+struct acc_row_t;   // no accumulate-ready tables for this curve
+#endif
 
 static_assert(sizeof(g1_affine_t) == 2 * 4 * Fq::N && sizeof(g1_xyzz_t) == 4 * 4 * Fq::N, "layout");
 static_assert(sizeof(abi_fr) == FR_BYTES && sizeof(abi_affine) == AFF_BYTES && sizeof(abi_proj) == 3 * 4 * Fq::N, "ABI layout");
@@ -170,8 +178,9 @@ __global__ __launch_bounds__(256) void k_digits(const fr_t *__restrict__ scalars
 
 // expanded base table of the precompute mode: out[j * n + i] = 2^(step * j) P_i in the converted form of k_convert_bases
 // (x R', y R' packed), j < factor; one lane per point, one inversion per table entry (a one-time cost per CRS)
-__global__ __launch_bounds__(128) void k_precompute_bases(const g1_affine_t *__restrict__ in, g1_affine_t *__restrict__ out, uint64_t n,
-                                                         int in_montgomery, uint32_t factor, uint32_t step) {
+template <class Out>
+__device__ __forceinline__ void precompute_bases_body(const g1_affine_t *__restrict__ in, Out *__restrict__ out, uint64_t n, int in_montgomery,
+                                                      uint32_t factor, uint32_t step) {
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     g1_affine_t p = tk_load(in + i);
@@ -198,9 +207,22 @@ __global__ __launch_bounds__(128) void k_precompute_bases(const g1_affine_t *__r
             a.x = Fq::mul(a.x, k);
             a.y = Fq::mul(a.y, k);
         }
-        tk_store(out + (uint64_t)j * n + i, a);
+        Out rec;
+        G1U::to_record(rec, a);
+        tk_store(out + (uint64_t)j * n + i, rec);
     }
 }
+__global__ __launch_bounds__(128) void k_precompute_bases(const g1_affine_t *__restrict__ in, g1_affine_t *__restrict__ out, uint64_t n,
+                                                         int in_montgomery, uint32_t factor, uint32_t step) {
+    precompute_bases_body(in, out, n, in_montgomery, factor, step);
+}
+#ifdef TK_MSM_SYM_PRECOMPUTE_ACC
+// the same table as accumulate-ready rows (ec_u.h), written directly: no second pass over the table
+__global__ __launch_bounds__(128) void k_precompute_bases_acc(const g1_affine_t *__restrict__ in, acc_row_t *__restrict__ out, uint64_t n,
+                                                             int in_montgomery, uint32_t factor, uint32_t step) {
+    precompute_bases_body(in, out, n, in_montgomery, factor, step);
+}
+#endif
 
 // grid (chunks, W); dynamic LDS = B * 4 bytes
 __global__ __launch_bounds__(1024) void k_hist(const uint32_t *__restrict__ dig, uint32_t *__restrict__ counts, msm_plan_t pl,
@@ -598,10 +620,14 @@ __device__ __forceinline__ uint32_t bucket_of(const uint32_t *__restrict__ bs, u
     return lo;
 }
 
-__global__ __launch_bounds__(256, 2) void k_accumulate_chunks(const g1_affine_t *__restrict__ bases, const uint32_t *__restrict__ sorted,
-                                                          const uint32_t *__restrict__ bstart, g1_xyzz_t *__restrict__ buckets,
-                                                          g1_xyzz_t *__restrict__ frag_head, g1_xyzz_t *__restrict__ frag_tail,
-                                                          msm_plan_t pl, uint32_t chunks_per_window) {
+// Row = g1_affine_t: the packed 96-byte converted record (every MSM but the table jobs of TKMK_BASES_ACC_READY); Row = acc_row_t: the
+// 128-byte accumulate-ready row of a resident commit table — the row number in the sorted record is the same, the stride and the loader
+// differ, and the sign of the entry goes into the addition instead of a negated copy of the base.
+template <class Row>
+__device__ __forceinline__ void accumulate_chunks_body(const Row *__restrict__ bases, const uint32_t *__restrict__ sorted,
+                                                       const uint32_t *__restrict__ bstart, g1_xyzz_t *__restrict__ buckets,
+                                                       g1_xyzz_t *__restrict__ frag_head, g1_xyzz_t *__restrict__ frag_tail,
+                                                       const msm_plan_t &pl, uint32_t chunks_per_window) {
     uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= pl.W * chunks_per_window) return;
     uint32_t w = gid / chunks_per_window, t = gid - w * chunks_per_window;
@@ -625,19 +651,25 @@ __global__ __launch_bounds__(256, 2) void k_accumulate_chunks(const g1_affine_t 
     // multiply-adds instead of in front of them.  (With every gather hitting the cache the kernel is 12.7 % faster: that is what the
     // two waves per SIMD do not hide by themselves.)
     uint32_t rec_next = s[lo], rec_next2 = lo + 1 < hi ? s[lo + 1] : 0u;
-    g1_affine_t raw = tk_load(bases + (rec_next & 0x7fffffffu));
+    Row raw = tk_load(bases + (rec_next & 0x7fffffffu));
     for (uint32_t k = lo; k < hi; k++) {
         const uint32_t rec = rec_next;
         G1U::A q;
-        const bool have = G1U::load_affine(q, raw);
+        bool have;
+        if constexpr (std::is_same<Row, g1_affine_t>::value) have = G1U::load_affine(q, raw);
+        else have = G1U::load_row(q, raw);
         rec_next = rec_next2;
         if (k + 1 < hi) {
             raw = tk_load(bases + (rec_next & 0x7fffffffu));
         }
         if (k + 2 < hi) rec_next2 = s[k + 2];
         if (have) {
-            if (rec & 0x80000000u) q = G1U::neg(q);
-            acc = G1U::add_mixed(acc, q);
+            if constexpr (std::is_same<Row, g1_affine_t>::value) {
+                if (rec & 0x80000000u) q = G1U::neg(q);
+                acc = G1U::add_mixed(acc, q);
+            } else {
+                acc = G1U::add_mixed_masked(acc, q, (uint32_t)((int32_t)rec >> 31));   // sign bit of the record -> mask
+            }
         }
         if (k + 1 == bend || k + 1 == hi) {  // the segment [seg_lo, k+1) of bucket b ends here
             bool whole = (seg_lo != lo || first_starts_here) && k + 1 == bend;   // a bucket begun in this chunk begins at seg_lo
@@ -658,6 +690,21 @@ __global__ __launch_bounds__(256, 2) void k_accumulate_chunks(const g1_affine_t 
         }
     }
 }
+
+__global__ __launch_bounds__(256, 2) void k_accumulate_chunks(const g1_affine_t *__restrict__ bases, const uint32_t *__restrict__ sorted,
+                                                          const uint32_t *__restrict__ bstart, g1_xyzz_t *__restrict__ buckets,
+                                                          g1_xyzz_t *__restrict__ frag_head, g1_xyzz_t *__restrict__ frag_tail,
+                                                          msm_plan_t pl, uint32_t chunks_per_window) {
+    accumulate_chunks_body(bases, sorted, bstart, buckets, frag_head, frag_tail, pl, chunks_per_window);
+}
+#ifdef TK_MSM_SYM_PRECOMPUTE_ACC
+__global__ __launch_bounds__(256, 2) void k_accumulate_chunks_rows(const acc_row_t *__restrict__ bases, const uint32_t *__restrict__ sorted,
+                                                               const uint32_t *__restrict__ bstart, g1_xyzz_t *__restrict__ buckets,
+                                                               g1_xyzz_t *__restrict__ frag_head, g1_xyzz_t *__restrict__ frag_tail,
+                                                               msm_plan_t pl, uint32_t chunks_per_window) {
+    accumulate_chunks_body(bases, sorted, bstart, buckets, frag_head, frag_tail, pl, chunks_per_window);
+}
+#endif
 
 // one lane per (window, bucket): gather the bucket's fragments.  big[0] = count, big[1 + i] = w * B + b
 __global__ __launch_bounds__(256) void k_combine(const uint32_t *__restrict__ bstart, g1_xyzz_t *__restrict__ buckets,
@@ -1182,10 +1229,18 @@ static uint32_t msm_resolve_c(uint32_t c_req, uint32_t n_src) {
     return c;
 }
 
+static hipError_t acc_kernels_set_lds(uint32_t bytes) {   // the dynamic-LDS claim is made on every accumulate kernel alike
+    hipError_t e = hipFuncSetAttribute((const void *)k_accumulate_chunks, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+#ifdef TK_MSM_SYM_PRECOMPUTE_ACC
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_accumulate_chunks_rows, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+#endif
+    return e;
+}
 static thread_local bool tl_background_batch = false;   // set by msm_pipeline for the jobs it enqueues
 static tkmk_error msm_enqueue(const fr_t *scalars, const g1_affine_t *bases_mont, uint32_t n_src, uint32_t factor, uint32_t c_req,
                               uint32_t bits, bool scalars_mont, hipStream_t s, g1_xyzz_t *wins_host, msm_plan_t *plan_out,
-                              msm_view_t sv = view_identity(), msm_view_t bv = view_identity(), uint32_t level_rows = 0) {
+                              msm_view_t sv = view_identity(), msm_view_t bv = view_identity(), uint32_t level_rows = 0,
+                              const acc_row_t *acc_rows = nullptr) {   // acc_rows: the table as accumulate-ready rows (bases_mont unused)
     msm_plan_t pl;
     static const bool force_one_pass = getenv("TKMK_MSM_ONE_PASS") != nullptr;
     pl.bits = bits;
@@ -1343,7 +1398,7 @@ static tkmk_error msm_enqueue(const fr_t *scalars, const g1_affine_t *bases_mont
     static const uint32_t acc_lds = [] {
         const char *e = getenv("TKMK_MSM_ACC_LDS");
         uint32_t v = e ? (uint32_t)atoi(e) : 0u;
-        if (v && hipFuncSetAttribute((const void *)k_accumulate_chunks, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v) != hipSuccess) v = 0;
+        if (v && acc_kernels_set_lds(v) != hipSuccess) v = 0;
         return v;
     }();
     // Batches issued on a caller stream marked BACKGROUND (tkmk_stream_set_background: a commit that nothing waits for until later, issued
@@ -1354,11 +1409,17 @@ static tkmk_error msm_enqueue(const fr_t *scalars, const g1_affine_t *bases_mont
     static const uint32_t bg_lds = [] {
         const char *e = getenv("TKMK_MSM_BACKGROUND_LDS");
         uint32_t v = e ? (uint32_t)atoi(e) : 98304u;
-        if (v && hipFuncSetAttribute((const void *)k_accumulate_chunks, hipFuncAttributeMaxDynamicSharedMemorySize, (int)v) != hipSuccess) v = 0;
+        if (v && acc_kernels_set_lds(v) != hipSuccess) v = 0;
         return v;
     }();
     const uint32_t lds_claim = (tl_background_batch && bg_lds) ? bg_lds : acc_lds;
     prof.mark("msm.prepare");   // bucket / queue memsets, the entry counter: keeps "msm.accumulate" to the kernel itself
+#ifdef TK_MSM_SYM_PRECOMPUTE_ACC
+    if (acc_rows)
+        hipLaunchKernelGGL(k_accumulate_chunks_rows, tk_div_up((size_t)pl.W * cpw, 256), 256, lds_claim, s, acc_rows, (const uint32_t *)d_sorted.p,
+                           (const uint32_t *)d_bstart.p, d_buckets.as<g1_xyzz_t>(), d_fh.as<g1_xyzz_t>(), d_ft.as<g1_xyzz_t>(), pl, cpw);
+    else
+#endif
     hipLaunchKernelGGL(k_accumulate_chunks, tk_div_up((size_t)pl.W * cpw, 256), 256, lds_claim, s, bases_mont, (const uint32_t *)d_sorted.p,
                        (const uint32_t *)d_bstart.p, d_buckets.as<g1_xyzz_t>(), d_fh.as<g1_xyzz_t>(), d_ft.as<g1_xyzz_t>(), pl, cpw);
     prof.mark("msm.accumulate");
@@ -1395,7 +1456,7 @@ static tkmk_error msm_enqueue(const fr_t *scalars, const g1_affine_t *bases_mont
         fprintf(stderr, "[msm debug] ptrs dig=%p sorted=%p counts=%p bstart=%p buckets=%p (+%zu) segs=%p (+%zu) wins=%p\n", d_dig.p,
                 d_sorted.p, d_counts.p, d_bstart.p, d_buckets.p, (size_t)pl.W * pl.B * sizeof(g1_xyzz_t), d_segs.p,
                 (size_t)pl.W * segs * sizeof(g1_xyzz_t), d_wins.p);
-    if (getenv("TKMK_MSM_DEBUG") && factor == 1 && view_is_identity(sv) && view_is_identity(bv) && !level_rows) TK_TRY(msm_debug_check(pl, scalars, bases_mont, d_dig.as<uint32_t>(), d_sorted.as<uint32_t>(),
+    if (getenv("TKMK_MSM_DEBUG") && factor == 1 && view_is_identity(sv) && view_is_identity(bv) && !level_rows && !acc_rows) TK_TRY(msm_debug_check(pl, scalars, bases_mont, d_dig.as<uint32_t>(), d_sorted.as<uint32_t>(),
                                                           d_bstart.as<uint32_t>(), d_buckets.as<g1_xyzz_t>(), s));
     TK_HIP(hipMemcpyAsync(wins_host, d_wins.p, wins_count * sizeof(g1_xyzz_t), hipMemcpyDeviceToHost, s));
     prof.finish();
@@ -1455,6 +1516,7 @@ struct msm_pipe_job {
     msm_view_t sv = view_identity(), bv = view_identity();   // operand views (tkmk_msm_multi_ex)
     uint32_t c = 0;               // window width of this job (0 = the call's)
     uint32_t level_rows = 0;      // rows per level of a precomputed TABLE the base view addresses (0 = the job's own expanded points)
+    bool acc_rows = false;        // `bases` is a table of accumulate-ready 128-byte rows (TKMK_BASES_ACC_READY table job; convert must be false)
 };
 // One pipeline set (streams, events, pinned result buffers, scratch arenas) per CALLER stream: batches issued on the same caller stream
 // run one after the other (the set's lock is held from the first launch to the last result), batches issued on different caller streams
@@ -1553,7 +1615,8 @@ static tkmk_error msm_pipeline(const std::vector<msm_pipe_job> &jobs, uint32_t c
             bm = d_bm.as<g1_affine_t>();
         }
         err = msm_enqueue(jb.scalars, bm, jb.n, jb.factor, jb.c ? jb.c : c_req, bits, scalars_mont, sl.s, sl.wins, &sl.pl, jb.sv,
-                          jb.convert ? view_identity() : jb.bv, jb.convert ? 0u : jb.level_rows);
+                          jb.convert ? view_identity() : jb.bv, jb.convert ? 0u : jb.level_rows,
+                          jb.acc_rows && !jb.convert ? (const acc_row_t *)jb.bases : nullptr);
         if (err != TKMK_SUCCESS) break;
         if (hipEventRecord(sl.done, sl.s) != hipSuccess) err = TKMK_ERR_UNKNOWN;
     }
@@ -1765,7 +1828,11 @@ static tkmk_error msm_ex_tiny(const abi_job_ex &jb, const tkmk_msm_config *cfg, 
 
 TK_API tkmk_error TK_MSM_SYM_MULTI_EX(const abi_job_ex *jobs, int n_jobs, const tkmk_msm_config *cfg, int bases_form, abi_proj *results) {
     if (!cfg || cfg->ext || cfg->batch_size != 1 || n_jobs < 0 || cfg->precompute_factor > 1) return TKMK_ERR_INVALID_ARGUMENT;
-    if (bases_form != TKMK_BASES_PLAIN && bases_form != TKMK_BASES_MONTGOMERY && bases_form != TKMK_BASES_CONVERTED) return TKMK_ERR_INVALID_ARGUMENT;
+    if (bases_form != TKMK_BASES_PLAIN && bases_form != TKMK_BASES_MONTGOMERY && bases_form != TKMK_BASES_CONVERTED && bases_form != TKMK_BASES_ACC_READY)
+        return TKMK_ERR_INVALID_ARGUMENT;
+    // TKMK_BASES_ACC_READY is decided per job: a table job reads 128-byte rows, every other job is taken as under TKMK_BASES_CONVERTED
+    const bool acc_ready = bases_form == TKMK_BASES_ACC_READY;
+    if (acc_ready) bases_form = TKMK_BASES_CONVERTED;
     if (cfg->bitsize < 0 || cfg->bitsize > 255 || cfg->c < 0 || cfg->c > MSM_MAX_C) return TKMK_ERR_INVALID_ARGUMENT;
     if (!cfg->are_scalars_on_device || !cfg->are_points_on_device) return TKMK_ERR_INVALID_ARGUMENT;   // views address resident tables
     if (n_jobs == 0) return TKMK_SUCCESS;
@@ -1787,10 +1854,16 @@ TK_API tkmk_error TK_MSM_SYM_MULTI_EX(const abi_job_ex *jobs, int n_jobs, const 
         if (jb.base_table_len >= (1ull << 31)) return TKMK_ERR_INVALID_ARGUMENT;   // 31-bit rows in the sort records
         if (jb.msm_size > 0 && jb.base_index && !jb.base_table_len) return TKMK_ERR_INVALID_ARGUMENT;   // an index list is never gathered unchecked
         if ((jb.table_c != 0) != (jb.table_factor != 0)) return TKMK_ERR_INVALID_ARGUMENT;
+        // TKMK_BASES_ACC_READY: a job with table_c > 0 IS a table job over 128-byte rows; a one-level table (table_factor 1) would be read
+        // as 96-byte records by the multi-window path, so it is refused instead
+        if (acc_ready && jb.table_c != 0 && jb.table_factor < 2) return TKMK_ERR_INVALID_ARGUMENT;
         if (jb.table_factor > 1) {   // precomputed table: resident form, known level size, a window width the sort can do at this size
             if (bases_form != TKMK_BASES_CONVERTED || !jb.base_table_len || jb.table_c < 2 || jb.table_c > MSM_MAX_C) return TKMK_ERR_INVALID_ARGUMENT;
             if (jb.base_table_len * jb.table_factor >= (1ull << 31)) return TKMK_ERR_INVALID_ARGUMENT;
             if (jb.table_c > 16 && (uint64_t)jb.msm_size * jb.table_factor < (1ull << 18)) return TKMK_ERR_INVALID_ARGUMENT;
+            if (acc_ready) {   // rows sit on line starts; a single term is not worth a table (the tiny path reads 96-byte records)
+                if (((uintptr_t)jb.bases & (ACC_ROW_BYTES - 1)) != 0 || jb.msm_size == 1) return TKMK_ERR_INVALID_ARGUMENT;
+            }
         }
     }
     tk_scratch d_flag;
@@ -1814,6 +1887,7 @@ TK_API tkmk_error TK_MSM_SYM_MULTI_EX(const abi_job_ex *jobs, int n_jobs, const 
             pjob.factor = jb.table_factor;
             pjob.c = jb.table_c;
             pjob.level_rows = (uint32_t)jb.base_table_len;
+            pjob.acc_rows = acc_ready;
         }
         pj.push_back(pjob);
         pj_index.push_back(j);
@@ -1892,5 +1966,37 @@ TK_API tkmk_error TK_MSM_SYM_PRECOMPUTE(const abi_affine *bases, int n_points, c
     TK_HIP(hipStreamSynchronize(s));
     return TKMK_SUCCESS;
 }
+
+#ifdef TK_MSM_SYM_PRECOMPUTE_ACC
+// The same table as accumulate-ready rows (TKMK_BASES_ACC_READY): n * F' records of 128 bytes, row r of the table at out + 128 r, written
+// on the device (`out` is device memory on a 128-byte boundary).  out == NULL: only *out_bytes is set.
+TK_API tkmk_error TK_MSM_SYM_PRECOMPUTE_ACC(const abi_affine *bases, uint64_t n_points, const tkmk_msm_config *cfg, void *out, uint64_t *out_bytes) {
+    if (!cfg || cfg->ext || n_points < 2 || n_points >= (1ull << 31) || cfg->bitsize < 0 || cfg->bitsize > 255 || cfg->c < 0 || cfg->c > MSM_MAX_C ||
+        cfg->precompute_factor < 1)
+        return TKMK_ERR_INVALID_ARGUMENT;
+    const uint32_t n = (uint32_t)n_points;
+    const uint32_t bits = cfg->bitsize ? (uint32_t)cfg->bitsize : (uint32_t)TK_MSM_SCALAR_BITS;
+    const uint32_t c = cfg->c ? (uint32_t)cfg->c : msm_resolve_c(0, n);
+    const uint32_t w_src = bits / c + 1;
+    uint32_t factor = (uint32_t)cfg->precompute_factor;
+    if (factor > w_src) factor = w_src;
+    if ((uint64_t)n * factor >= (1ull << 31)) return TKMK_ERR_INVALID_ARGUMENT;
+    if (out_bytes) *out_bytes = (uint64_t)n * factor * ACC_ROW_BYTES;
+    if (!out) return out_bytes ? TKMK_SUCCESS : TKMK_ERR_INVALID_POINTER;
+    if (!bases) return TKMK_ERR_INVALID_POINTER;
+    if (((uintptr_t)out & (ACC_ROW_BYTES - 1)) != 0) return TKMK_ERR_INVALID_ARGUMENT;
+    TK_TRY(tk_require_device());
+    const uint32_t wg = (w_src + factor - 1) / factor;
+    hipStream_t s = tk_stream(cfg->stream_handle);
+    tk_frame frame(s);
+    tk_staged P;
+    TK_TRY(P.in(bases, (size_t)n * AFF_BYTES, cfg->are_points_on_device, s));
+    hipLaunchKernelGGL(k_precompute_bases_acc, tk_div_up(n, 128), 128, 0, s, (const g1_affine_t *)P.dev, (acc_row_t *)out, (uint64_t)n,
+                       cfg->are_points_montgomery_form ? 1 : 0, factor, c * wg);
+    TK_HIP(hipGetLastError());
+    TK_HIP(hipStreamSynchronize(s));
+    return TKMK_SUCCESS;
+}
+#endif
 
 }  // namespace TK_MSM_NS

@@ -1008,8 +1008,14 @@ inline CommitComm &commit_comm() {
     return c;
 }
 
+// one row of a commit table in the accumulate-ready form (include/tkmk.h: TKMK_BASES_ACC_READY; opaque here)
+struct alignas(128) AccRow {
+    unsigned char bytes[128];
+};
+
 class Sigma1 {
-    DeviceVec<G1Affine> xy_powers_;   // level 0: the table in resident form; with table_c_: levels 1 .. table_factor_ - 1 behind it
+    DeviceVec<G1Affine> xy_powers_;   // level 0 in resident (converted) 96-byte form: small commits, level0(), the G1 NTT of the Lagrange twin
+    DeviceVec<AccRow> table_;         // with table_c_: ALL table_factor_ levels as accumulate-ready 128-byte rows (the table jobs' bases)
     size_t rs_x_, rs_y_;              // the GRID (all ranks' columns); this rank holds local_cols_ of its rs_y_ columns, all rs_x_ rows
     uint32_t table_c_ = 0, table_factor_ = 0;
     Shard shard_;
@@ -1020,7 +1026,8 @@ class Sigma1 {
     // table_c > 0 (a resident prover that amortises it over many proofs): the table is expanded ONCE into its 2^(table_c j)
     // multiples (ICICLE's msm_precompute_bases, MSMConfig::precompute_factor — left at 1 by the reference), so that every large
     // commit runs as ONE bucket set with table_c-bit windows: 13 instead of 16 bucket additions per point at table_c = 20.
-    // HBM: windows x the table (2^24 points at table_c = 20: 21 GB of the 288).
+    // The table is held as accumulate-ready rows (128 bytes each, written directly by the precompute kernel) next to the 96-byte level 0.
+    // HBM: windows x the table x 128 / 96 (2^24 points at table_c = 20: 27.9 GB of the 288) + the 1.6 GB level 0.
     // shard.world > 1: `xy_powers` holds THIS RANK'S columns only (cols_of_grid(...) below cuts them out of a whole grid), row-major
     // rs_x x local_cols; rs_y_size stays the grid's width.
     Sigma1(DeviceVec<G1Affine> &&xy_powers, size_t rs_x_size, size_t rs_y_size, uint32_t table_c = 0, Shard shard = Shard{})
@@ -1032,15 +1039,18 @@ class Sigma1 {
         if (table_c >= 2 && xy_powers_.len() >= 2) {
             const uint32_t windows = 255 / table_c + 1;
             if ((uint64_t)xy_powers_.len() * windows >= (1ull << 31)) throw Error("xy_powers is too large for a precomputed table");
-            DeviceVec<G1Affine> table(xy_powers_.len() * windows);
-            cfg.c = (int)table_c;
-            cfg.precompute_factor = (int)windows;
-            check(bls12_381_msm_precompute_bases(xy_powers_.ptr(), (int)xy_powers_.len(), &cfg, table.ptr()), "msm::precompute_bases");
-            xy_powers_ = std::move(table);
+            tkmk_msm_config tcfg = cfg;
+            tcfg.c = (int)table_c;
+            tcfg.precompute_factor = (int)windows;
+            uint64_t bytes = 0;
+            check(bls12_381_msm_precompute_bases_acc(xy_powers_.ptr(), xy_powers_.len(), &tcfg, nullptr, &bytes), "msm::precompute_bases_acc (size)");
+            if (bytes != (uint64_t)xy_powers_.len() * windows * sizeof(AccRow)) throw Error("unexpected size of the accumulate-ready commit table");
+            DeviceVec<AccRow> table(xy_powers_.len() * windows);
+            check(bls12_381_msm_precompute_bases_acc(xy_powers_.ptr(), xy_powers_.len(), &tcfg, table.ptr(), nullptr), "msm::precompute_bases_acc");
+            table_ = std::move(table);
             table_c_ = table_c, table_factor_ = windows;
-        } else {
-            check(bls12_381_msm_convert_bases(xy_powers_.ptr(), xy_powers_.len(), &cfg, xy_powers_.ptr()), "msm::convert_bases");
         }
+        check(bls12_381_msm_convert_bases(xy_powers_.ptr(), xy_powers_.len(), &cfg, xy_powers_.ptr()), "msm::convert_bases");   // after the table: it reads the plain records
     }
     size_t rs_x() const { return rs_x_; }
     size_t rs_y() const { return rs_y_; }
@@ -1071,6 +1081,11 @@ class Sigma1 {
         return out;
     }
     uint32_t table_c() const { return table_c_; }
+    // a table job: the same rows, addressed in the accumulate-ready table (run_jobs passes TKMK_BASES_ACC_READY, decided per job)
+    void use_table(tkmk_msm_job_ex &j) const {
+        j.bases = reinterpret_cast<const G1Affine *>(table_.ptr());
+        j.table_c = table_c_, j.table_factor = table_factor_;
+    }
     // the MSM job of one commit: coefficient box x CRS sub-grid, both as views (msm_size 0 for the zero polynomial)
     tkmk_msm_job_ex job(DensePolynomialExt &poly, const char *name = nullptr) const {
         // the box the MSM runs over: the polynomial's degree bound (DensePolynomialExt::shape_degree) — or its MEASURED degree when the
@@ -1103,7 +1118,7 @@ class Sigma1 {
         j.base_table_len = table_len();
         // large commits through the expanded table; small ones (the wide windows' two-pass sort needs 2^18 entries, and a 2^19-bucket
         // reduction is not worth paying for a few thousand points) through level 0 with the ordinary multi-window path
-        if (table_c_ && (uint64_t)tx * mine * table_factor_ >= (1ull << 20)) j.table_c = table_c_, j.table_factor = table_factor_;
+        if (table_c_ && (uint64_t)tx * mine * table_factor_ >= (1ull << 20)) use_table(j);
         return j;
     }
     static G1Affine to_affine(const tkmk_g1_projective &res) {
@@ -1131,8 +1146,8 @@ class Sigma1 {
             host_trace("commit batch of %zu:%s", jobs.size(), d.c_str());
         }
         const CommitComm &cc = commit_comm();
-        if (cc.comm) check(cc.multi_ex_sharded(cc.comm, jobs.data(), (int)jobs.size(), &cfg, TKMK_BASES_CONVERTED, res.data()), "tkmk_msm_multi_ex_sharded");
-        else check(tkmk_msm_multi_ex(jobs.data(), (int)jobs.size(), &cfg, TKMK_BASES_CONVERTED, res.data()), "tkmk_msm_multi_ex");
+        if (cc.comm) check(cc.multi_ex_sharded(cc.comm, jobs.data(), (int)jobs.size(), &cfg, TKMK_BASES_ACC_READY, res.data()), "tkmk_msm_multi_ex_sharded");
+        else check(tkmk_msm_multi_ex(jobs.data(), (int)jobs.size(), &cfg, TKMK_BASES_ACC_READY, res.data()), "tkmk_msm_multi_ex");
         std::vector<G1Affine> out;
         for (auto &r : res) out.push_back(to_affine(r));
         return out;
@@ -1152,7 +1167,7 @@ class Sigma1 {
         j.bases = xy_powers_.ptr();
         j.msm_size = (int)(rs_x_ * rs_y_);
         j.base_table_len = table_len();
-        if (table_c_ && (uint64_t)rs_x_ * rs_y_ * table_factor_ >= (1ull << 20)) j.table_c = table_c_, j.table_factor = table_factor_;
+        if (table_c_ && (uint64_t)rs_x_ * rs_y_ * table_factor_ >= (1ull << 20)) use_table(j);
         return j;
     }
     // The Lagrange-basis twin of the grid [0, xs) x [0, ys) of this table: [L_i(tau_x) L_j(tau_y)] G = (1 / N) x the inverse NTT over G1

@@ -86,7 +86,7 @@ SYMBOLS = [
     "tkmk_device_count", "tkmk_set_device", "tkmk_get_available_memory", "tkmk_malloc", "tkmk_malloc_async", "tkmk_free",
     "tkmk_free_async", "tkmk_memcpy_h2d", "tkmk_memcpy_d2h", "tkmk_memcpy_d2d", "tkmk_memcpy_h2d_async",
     "tkmk_memcpy_d2h_async", "tkmk_memcpy_2d_d2d", "tkmk_memset", "tkmk_stream_create", "tkmk_stream_synchronize", "tkmk_stream_destroy", "tkmk_stream_set_background",
-    "tkmk_device_synchronize", "tkmk_release_scratch", "tkmk_error_string", "tkmk_is_hip_build", "tkmk_keccak256", "tkmk_r1cs_index", "tkmk_msm_default_config", "bls12_381_msm", "bls12_381_g2_msm", "tkmk_g1_ntt", "tkmk_g1_ntt_axes", "tkmk_g1_prefix_sums", "tkmk_g1_scale", "bls12_381_msm_precompute_bases", "bn254_msm_precompute_bases", "tkmk_msm_multi", "bn254_msm", "tkmk_bn254_msm_multi", "bn254_get_root_of_unity", "bn254_ntt_init_domain", "bn254_ntt_release_domain",
+    "tkmk_device_synchronize", "tkmk_release_scratch", "tkmk_error_string", "tkmk_is_hip_build", "tkmk_keccak256", "tkmk_r1cs_index", "tkmk_msm_default_config", "bls12_381_msm", "bls12_381_g2_msm", "tkmk_g1_ntt", "tkmk_g1_ntt_axes", "tkmk_g1_prefix_sums", "tkmk_g1_scale", "bls12_381_msm_precompute_bases", "bls12_381_msm_precompute_bases_acc", "bn254_msm_precompute_bases", "tkmk_msm_multi", "bn254_msm", "tkmk_bn254_msm_multi", "bn254_get_root_of_unity", "bn254_ntt_init_domain", "bn254_ntt_release_domain",
     "bn254_ntt", "tkmk_bn254_bintt", "tkmk_bn254_fr_random_device",
     "tkmk_bn254_g1_batch_scalar_mul_device",
     "tkmk_ntt_default_config", "bls12_381_get_root_of_unity", "bls12_381_ntt_init_domain", "bls12_381_ntt_release_domain",
@@ -413,6 +413,23 @@ def msm_precompute_bases(bases, n, factor, c=0, bitsize=0, curve="bls12_381", po
     return out
 
 
+def msm_precompute_bases_acc(bases, n, factor, c=0, bitsize=0, points_montgomery=False):
+    """-> DeviceBuffer with the same table as accumulate-ready 128-byte rows: the `bases` of a table job of
+    msm_multi_ex(..., bases_form=BASES_ACC_READY) (bls12_381_msm_precompute_bases_acc; the library reports the size)"""
+    cfg = lib().tkmk_msm_default_config()
+    cfg.precompute_factor = factor
+    cfg.c, cfg.bitsize = c, bitsize
+    cfg.are_points_on_device = _on_dev(bases)
+    cfg.are_points_montgomery_form = points_montgomery
+    cfg.are_results_on_device = True
+    nbytes = ctypes.c_uint64(0)
+    fn = lib().bls12_381_msm_precompute_bases_acc
+    _check(fn(_p(bases), ctypes.c_uint64(n), ctypes.byref(cfg), None, ctypes.byref(nbytes)), "bls12_381_msm_precompute_bases_acc")
+    out = DeviceBuffer(nbytes.value)
+    _check(fn(_p(bases), ctypes.c_uint64(n), ctypes.byref(cfg), _p(out), None), "bls12_381_msm_precompute_bases_acc")
+    return out
+
+
 def msm(scalars, bases, msm_size=None, batch=1, shared_points=True, c=0, bitsize=0, stream=None, curve="bls12_381",
         precompute_factor=1, scalars_montgomery=False, points_montgomery=False):
     """returns `batch` projective results (144 B each; 96 B for bn254) on the host"""
@@ -526,7 +543,7 @@ class MsmJobEx(ctypes.Structure):
                 ("table_c", ctypes.c_uint32), ("table_factor", ctypes.c_uint32)]
 
 
-BASES_PLAIN, BASES_MONTGOMERY, BASES_CONVERTED = 0, 1, 2
+BASES_PLAIN, BASES_MONTGOMERY, BASES_CONVERTED, BASES_ACC_READY = 0, 1, 2, 3
 
 
 def msm_convert_bases(bases, n=None, points_montgomery=False, out=None):

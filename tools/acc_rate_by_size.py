@@ -7,7 +7,9 @@ a 8192 x 2048 grid, as the resident prover holds it), alone on the device (one p
   * the measured k_accumulate_chunks time (HIP events on the launch stream) and the additions the library counted on the device.
 Scalars: dense uniform 255-bit (the quotient polynomials), 'small' (values below 2^20 with 30 % zeros: the A.w / B.w / C.w evaluations) and
 'sparse' (6 % non-zero: b's evaluations).  Prints one JSON line per shape and a summary.
-usage (GPU box): python tools/acc_rate_by_size.py [--reps 3]"""
+--row-format 96 (default): the table as 96-byte converted records (msm_precompute_bases, BASES_CONVERTED); 128: the same table as
+accumulate-ready 128-byte rows (msm_precompute_bases_acc, BASES_ACC_READY), as the resident prover holds it.
+usage (GPU box): python tools/acc_rate_by_size.py [--reps 3] [--row-format 96|128]"""
 import argparse
 import json
 import os
@@ -33,6 +35,7 @@ def plan(entries_upper, n_expanded):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--row-format", type=int, choices=(96, 128), default=96)
     args = ap.parse_args()
     import tkmk
     tkmk.set_device(0)
@@ -47,7 +50,10 @@ def main():
     h = tkmk.fr_random_device(0x746F6B01, n_table)
     bases = tkmk.g1_batch_scalar_mul_device(h, gen, n_table)
     h.free()
-    table = tkmk.msm_precompute_bases(bases, n_table, windows, c=c)
+    if args.row_format == 128:
+        table, form = tkmk.msm_precompute_bases_acc(bases, n_table, windows, c=c), tkmk.BASES_ACC_READY
+    else:
+        table, form = tkmk.msm_precompute_bases(bases, n_table, windows, c=c), tkmk.BASES_CONVERTED
     bases.free()
     dense = tkmk.fr_random_device(0x746F6B02, n_table)
     host = dense.to_host(32 * rs_y * 4097).reshape(-1, 32).copy()       # the 4097 x 2048 corner is enough for the small / sparse kinds
@@ -65,13 +71,13 @@ def main():
     out = []
     for name, tx, ty, sc in shapes:
         job = dict(scalars=sc, bases=table, n=tx * ty, scalar_view=(ty, rs_y), base_view=(ty, rs_y), table_len=n_table, table=(c, windows))
-        tkmk.msm_multi_ex([job], bases_form=tkmk.BASES_CONVERTED)
+        tkmk.msm_multi_ex([job], bases_form=form)
         tkmk.synchronize()
         tkmk.profile_enable(True)
         tkmk.profile_reset()
         tkmk.native_stats_reset()
         for _ in range(args.reps):
-            tkmk.msm_multi_ex([job], bases_form=tkmk.BASES_CONVERTED)
+            tkmk.msm_multi_ex([job], bases_form=form)
         tkmk.synchronize()
         tkmk.profile_enable(False)
         ms, cnt = tkmk.profile_get("msm.accumulate")
@@ -82,14 +88,14 @@ def main():
         busy_lanes = -(-int(adds) // chunk)                              # lanes whose chunk holds entries
         rounds = -(-busy_lanes // SLOTS)
         last = busy_lanes - (rounds - 1) * SLOTS
-        rec = {"commit": name, "box": [tx, ty], "points": tx * ty, "entries": int(adds), "entries_upper_bound": n_exp, "chunk": chunk,
+        rec = {"row_format": args.row_format, "commit": name, "box": [tx, ty], "points": tx * ty, "entries": int(adds), "entries_upper_bound": n_exp, "chunk": chunk,
                "lanes_launched": lanes, "lanes_with_work": busy_lanes, "rounds": rounds, "last_round_fill": round(last / SLOTS, 4),
                "accumulate_ms": round(ms / cnt, 3), "additions_per_s": round(adds / (ms / cnt * 1e-3) / 1e9, 3)}
         out.append(rec)
         print(json.dumps(rec), flush=True)
     tot_adds = sum(r["entries"] for r in out[:6])
     tot_ms = sum(r["accumulate_ms"] for r in out[:6])
-    print(json.dumps({"summary": "dense quotient commits of one proof", "additions": tot_adds, "accumulate_ms": round(tot_ms, 2),
+    print(json.dumps({"summary": "dense quotient commits of one proof", "row_format": args.row_format, "additions": tot_adds, "accumulate_ms": round(tot_ms, 2),
                       "additions_per_s_e9": round(tot_adds / tot_ms / 1e6, 3)}))
 
 
