@@ -71,15 +71,16 @@ typedef struct { tkmk_fq x, y; } tkmk_g1_affine;          /* G1Affine  (96 B)  *
 typedef struct { tkmk_fq x, y, z; } tkmk_g1_projective;   /* G1Projective (144 B) */
 typedef void *tkmk_stream;                                /* IcicleStream handle (a hipStream_t) */
 
-/* THE ONE DECLARED CONVENTION THAT IS AN INFERENCE, NOT A PIN ("parity unpinned"): the generator g of the
- * scalar field's two-adic subgroup, omega_{2^32} = g^((r-1)/2^32).  bls12_381_get_root_of_unity, the oracle, the Python
- * restatements and the setup all derive their root of unity from THIS constant.  The reference takes the root from ICICLE
- * (ntt::get_root_of_unity, libs/src/bivariate_polynomial/mod.rs:47-52; not in the tree).  5 = ffjavascript's rule (smallest
- * quadratic non-residue), which the reference's browser prover / verifier use on the native prover's outputs;
- * 7 = arkworks / zkcrypto's constant.  Both generate the subgroup and pass every self-consistency test; they order the domain
- * differently, so a wrong choice is silent within this repository and fatal against a reference-made CRS.  If ICICLE's constant
- * turns out to be 7^((r-1)/2^32): change this line (tests/test_root_convention.py proves the switch green), or set the
- * environment variable TKMK_FR_ROOT_GENERATOR=7 for a process (the same variable is honoured by the oracle and the Python refs). */
+/* THE ONE CONVENTION THAT IS AN INFERENCE, NOT A PIN: the generator g of the scalar field's two-adic subgroup,
+ * omega_{2^32} = g^((r-1)/2^32).  The reference takes the root from ICICLE (ntt::get_root_of_unity,
+ * libs/src/bivariate_polynomial/mod.rs:47-52; not in the tree).  5 = ffjavascript's rule (smallest quadratic non-residue), which the
+ * reference's browser prover / verifier use on the native prover's outputs; 7 = arkworks / zkcrypto's constant.
+ * Both generate the subgroup and pass every self-consistency test; they order the domain differently, so a proof made under one is
+ * rejected against a CRS made under the other.  This constant is the DEFAULT: bls12_381_get_root_of_unity, the oracle, the Python
+ * restatements and the setup start from it.  The prover and `preprocess` no longer trust it: they IDENTIFY the generator per CRS
+ * (tkmk_crs_identify_root below: lagrange_KL follows from xy_powers under exactly one of {5, 7}) and adopt it with
+ * tkmk_ntt_set_root_generator, or refuse the CRS.  The environment variable TKMK_FR_ROOT_GENERATOR=<g> sets the initial value of a
+ * process (the oracle and the Python refs honour the same variable) and PINS it: a prover that finds it set tries that generator only. */
 #define TKMK_BLS12_381_FR_ROOT_GENERATOR 5
 
 /* ---------------------------------------------------------------------------------------------
@@ -251,6 +252,21 @@ tkmk_error bls12_381_msm_convert_bases(const tkmk_g1_affine *bases, uint64_t n, 
  * (TKMK_ERR_INVALID_ARGUMENT otherwise), whatever cfg->are_results_on_device says; `bases` follows cfg->are_points_on_device. */
 tkmk_error bls12_381_msm_precompute_bases_acc(const tkmk_g1_affine *bases, uint64_t n, const tkmk_msm_config *cfg, void *out, uint64_t *out_bytes);
 
+/* Which root of unity was this reference string made under?  The CRS carries lagrange_KL = [L_{s_max-1}(tau_y) K_{m_I-1}(tau_x)] G
+ * (libs/src/group_structures/mod.rs:326-327), and L_{n-1}(X) = (1/n) sum_j w_n^j X^j, so
+ *     lagrange_KL = sum_{a < m_i} sum_{b < s_max} (w_x^a / m_i) (w_y^b / s_max) xy_powers[a * rs_y + b]
+ * with w_x, w_y the roots of order m_i, s_max under the generator the CRS was made with.  For every candidates[c] (a generator as in
+ * bls12_381_get_root_of_unity_with_generator; a quadratic residue is refused) this writes that sum over the columns b = col0 + col_step * k
+ * < s_max to partial_out[c] (HOST, canonical projective like every MSM result): one scalar grid per candidate (tkmk_poly_geometric_grid)
+ * and ONE tkmk_msm_multi_ex batch over a view of the table — plain windows, no precomputed table, nothing copied.  xy_powers_dev: device,
+ * h_max rows of rs_y records in the form bases_form names (TKMK_BASES_PLAIN / _MONTGOMERY right after the upload, _CONVERTED later).
+ * (col0, col_step) = (0, 1) is the whole corner; (rank, G) is a sharded rank's share, and the shares add up to the whole sum.  The entry
+ * does not compare: the caller adds partials where sharded and compares with the CRS's lagrange_KL record.  m_i and s_max are powers of
+ * two, m_i <= h_max, s_max <= rs_y, h_max * rs_y < 2^31, 1 <= n_candidates <= 8.  No state is read or changed (the generator in
+ * effect and the NTT domain play no part).  When m_i <= 2 and s_max <= 2 every generator gives the same sums (both roots are -1). */
+tkmk_error tkmk_crs_identify_root(const tkmk_g1_affine *xy_powers_dev, int bases_form, uint32_t h_max, uint32_t rs_y, uint32_t m_i, uint32_t s_max,
+                                  uint32_t col0, uint32_t col_step, const uint32_t *candidates, int n_candidates, tkmk_g1_projective *partial_out);
+
 /* ---------------------------------------------------------------------------------------------
  * NTT — replaces icicle_core::ntt::{ntt, initialize_domain, release_domain, get_root_of_unity}
  * (extern "C" bls12_381_ntt, _ntt_init_domain, _ntt_release_domain, _get_root_of_unity) as called at
@@ -280,6 +296,16 @@ typedef struct {
 
 tkmk_ntt_config tkmk_ntt_default_config(void);            /* NTTConfig::default() */
 tkmk_error bls12_381_get_root_of_unity(uint64_t max_size, tkmk_fr *rou_out);
+/* The same under a named generator g (omega_{2^32} = g^((r-1)/2^32)): pure host arithmetic, reads and changes no state.  A quadratic
+ * residue (g = 4, ...) is refused with TKMK_ERR_INVALID_ARGUMENT exactly as bls12_381_get_root_of_unity refuses one. */
+tkmk_error bls12_381_get_root_of_unity_with_generator(uint32_t g, uint64_t max_size, tkmk_fr *rou_out);
+/* The generator bls12_381_get_root_of_unity derives from at this moment: TKMK_BLS12_381_FR_ROOT_GENERATOR, the value of
+ * TKMK_FR_ROOT_GENERATOR when the process started with one, or the last successful tkmk_ntt_set_root_generator. */
+tkmk_error tkmk_ntt_root_generator(uint32_t *g);
+/* Replaces it, process-wide (BLS12-381 only).  TKMK_ERR_INVALID_ARGUMENT while a domain is initialised — its tables were built under the
+ * generator in effect: bls12_381_ntt_release_domain first — and for a quadratic residue; naming the generator in effect always succeeds.
+ * Everything a host derived from the old root (domains, Lagrange tables, a resident prover context) is the caller's to rebuild. */
+tkmk_error tkmk_ntt_set_root_generator(uint32_t g);
 /* primitive_root must have order 2^k; builds twiddles for sizes up to 2^k. Fails if a domain exists. */
 tkmk_error bls12_381_ntt_init_domain(const tkmk_fr *primitive_root, const tkmk_ntt_init_domain_config *cfg);
 tkmk_error bls12_381_ntt_release_domain(void);
@@ -454,6 +480,12 @@ tkmk_error tkmk_poly_find_degree(const tkmk_fr *coeffs_dev, uint32_t x_size, uin
  * off = (0,0); mul_monomial (mod.rs:1820-1844) is off = (x_exponent, y_exponent) */
 tkmk_error tkmk_poly_place(const tkmk_fr *src_dev, uint32_t sx, uint32_t sy, tkmk_fr *dst_dev, uint32_t dx, uint32_t dy,
                            uint32_t off_x, uint32_t off_y, tkmk_stream stream);
+/* out_dev (rows x cols, fully written, canonical) [i][k] = c0 * gx^i * gy^(col0 + col_step * k), 0^0 = 1; c0, gx, gy are host scalars.
+ * There is NO input array (the grids the reference makes by scaling a matrix of ones: Permutation::to_poly's identity part,
+ * libs/src/iotools/mod.rs:419-437; the setup's monomial grid): nothing crosses PCIe.  col0 / col_step give a sharded rank its COLS slice
+ * directly (local column k = global column rank + G k).  col0 + col_step * (cols - 1) must be < 2^32 (TKMK_ERR_INVALID_ARGUMENT). */
+tkmk_error tkmk_poly_geometric_grid(uint32_t rows, uint32_t cols, const tkmk_fr *c0, const tkmk_fr *gx, const tkmk_fr *gy, uint32_t col0,
+                                    uint32_t col_step, tkmk_fr *out_dev, tkmk_stream stream);
 /* dst[i][j] = src[i][j] * factor_x^i * factor_y^j (_scale_coeffs, mod.rs:1567-1613; NULL factor = 1); in place ok */
 tkmk_error tkmk_poly_scale_coeffs(const tkmk_fr *src_dev, uint32_t x_size, uint32_t y_size, const tkmk_fr *factor_x,
                                   const tkmk_fr *factor_y, tkmk_fr *dst_dev, tkmk_stream stream);

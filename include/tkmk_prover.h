@@ -44,7 +44,16 @@ typedef struct {          /* seconds */
  * sums in prove1's walk order 5.2 GB; the binding tables 4.2 GB; the subcircuit library and the NTT domain < 1 GB — 36 GB of the 288 —
  * and 7.6 s at open (2.7 s table expansion, 3.3 s group NTT behind the Lagrange table, 1.3 s prefix sums and their expansion; production
  * shape 1.9 s).  TKMK_PROVER_LAGRANGE=0 drops the second and third items (U, V, W, B, R are then committed from coefficients).  A
- * sharded context (tkmk_prover_open_sharded) keeps 1 / G of the first three per GPU and does 1 / G of their one-time work. */
+ * sharded context (tkmk_prover_open_sharded) keeps 1 / G of the first three per GPU and does 1 / G of their one-time work.
+ * THE ROOT OF UNITY IS IDENTIFIED FROM THE CRS, not assumed (tkmk.h: TKMK_BLS12_381_FR_ROOT_GENERATOR, tkmk_crs_identify_root): right after
+ * xy_powers is uploaded, and before anything that depends on omega is built, lagrange_KL is recomputed from the m_I x s_max corner of
+ * xy_powers under the generator in effect and under the other of {5, 7} — one plain-window MSM of m_I * s_max points and one scalar grid
+ * per candidate (DESIGN.md section 5 has the measured cost).  Exactly one reproduces the CRS's record: if it is not the generator in
+ * effect, the process-wide NTT domain is released and the generator replaced (tkmk_ntt_set_root_generator) — refused with
+ * TKMK_ERR_INVALID_ARGUMENT while ANOTHER prover context of the process is open, since that one was built under the generator in effect.
+ * None does: TKMK_ERR_INVALID_ARGUMENT, the message names every generator tried; no context is made.  Both do (m_I <= 2 and s_max <= 2):
+ * the generator in effect stays.  TKMK_FR_ROOT_GENERATOR=<g> in the environment PINS the convention: that generator alone is tried.
+ * tkmk_prover_root_generator tells which generator a context runs under. */
 tkmk_error tkmk_prover_open(const char *subcircuit_library_dir, const char *crs_dir, tkmk_prover **out);
 /* ONE proof over the G GPUs of a node (the reference is single-device, so nothing is replaced).  G is a power of
  * two, at most min(n, m_I, s_max).  Rank r of the communicator `comm` (a tkmk_comm of include/tkmk_dist.h, made by the host: one process
@@ -57,6 +66,8 @@ tkmk_error tkmk_prover_open(const char *subcircuit_library_dir, const char *crs_
  * from the same gathered commitments) and the small polynomials built from host values.  Exchanges per proof: one all-gather per commit
  * batch (144 B per commitment + a status block), one all-to-all per transform, a ring shift per Y-shifted term, all-gathers of a few
  * values (evaluation partials, remainder rows), one broadcast of rank 0's blinding scalars; DESIGN.md section 6 counts them.
+ * The root-of-unity check of tkmk_prover_open runs on every rank over its own columns of the corner; one all-gather carries the partial
+ * sums, every rank adds them and reaches the same decision: an adoption or a refusal is every rank's.
  * Every rank must call _open_sharded and then every _prove / _prove_ex with the same arguments; every rank gets the same proof, byte for
  * byte the one the single-GPU context gives for the same blinding scalars (tests/test_gpu_sharded_prover.py, G = 2, 4, 8 over the
  * loopback transport); RANK 0 ALONE writes <output_dir>/proof.json (temporary file + rename), after all ranks agreed that they
@@ -90,6 +101,8 @@ void tkmk_prover_free_string(char *s);
 const char *tkmk_prover_last_error(void);   /* message of the last failed call on this thread */
 /* where the context's reference string came from: "combined_sigma.rkyv" or "combined_sigma.tkcrs" */
 const char *tkmk_prover_crs_source(const tkmk_prover *p);
+/* the root-of-unity generator the context runs under: the one its reference string was made under (see tkmk_prover_open) */
+uint32_t tkmk_prover_root_generator(const tkmk_prover *p);
 
 #ifdef __cplusplus
 }

@@ -14,6 +14,9 @@
 #define TK_NTT_FR_PARAMS bls12_381_fr_params
 #define TK_NTT_ABI_FR tkmk_fr
 #define TK_NTT_SYM_ROOT bls12_381_get_root_of_unity
+#define TK_NTT_SYM_ROOT_WITH_GENERATOR bls12_381_get_root_of_unity_with_generator
+#define TK_NTT_SYM_GET_GENERATOR tkmk_ntt_root_generator
+#define TK_NTT_SYM_SET_GENERATOR tkmk_ntt_set_root_generator
 #define TK_NTT_SYM_INIT bls12_381_ntt_init_domain
 #define TK_NTT_SYM_RELEASE bls12_381_ntt_release_domain
 #define TK_NTT_SYM_DOMAIN_SIZE bls12_381_ntt_domain_size

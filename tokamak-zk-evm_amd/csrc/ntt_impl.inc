@@ -197,9 +197,38 @@ static void fr_to_api(abi_fr *o, const fr_t &x) {
 }
 // w_{2^TWO_ADICITY} = g^((r-1) >> TWO_ADICITY) in Montgomery form, g = TK_NTT_ROOT_GENERATOR (include/tkmk.h declares it for the
 // reference's field and says why it is a declared convention); TK_NTT_ROOT_GENERATOR_ENV, when the instantiation names one, lets a
-// process choose another quadratic non-residue (tests/test_root_convention.py).  Host arithmetic, computed once.
-static fr_t fr_root_top() {
-    static const fr_t top = [] {
+// process choose another quadratic non-residue for the INITIAL value (tests/test_root_convention.py); TK_NTT_SYM_SET_GENERATOR, when
+// the instantiation names it, replaces the value afterwards (the prover adopts the generator a CRS was made under).  Host arithmetic.
+static fr_t fr_root_top_of(uint32_t g) {
+    uint32_t ex[Fr::N];   // (r - 1) >> TWO_ADICITY
+    for (int i = 0; i < Fr::N; i++) ex[i] = FrP::MOD[i];
+    ex[0] -= 1;           // r is odd: no borrow
+    const int sh = FrP::TWO_ADICITY;
+    uint32_t q[Fr::N];
+    for (int i = 0; i < Fr::N; i++) {
+        int src = i + sh / 32;
+        uint64_t lo = src < Fr::N ? ex[src] : 0, hi = src + 1 < Fr::N ? ex[src + 1] : 0;
+        q[i] = (uint32_t)(((hi << 32) | lo) >> (sh % 32));
+    }
+    fr_t base = Fr::zero();
+    base.l[0] = g;
+    base = Fr::to_mont(base);
+    fr_t acc = Fr::zero();
+    acc.l[0] = 1;
+    acc = Fr::to_mont(acc);
+    for (int bit = 32 * Fr::N - 1; bit >= 0; bit--) {
+        acc = Fr::sqr(acc);
+        if ((q[bit >> 5] >> (bit & 31)) & 1) acc = Fr::mul(acc, base);
+    }
+    return acc;
+}
+// the generator in effect and its w_{2^TWO_ADICITY}: read and replaced under g_dom_mu
+struct root_state_t {
+    uint32_t g;
+    fr_t top;
+};
+static root_state_t &fr_root_state() {   // g_dom_mu held by the caller
+    static root_state_t st = [] {
         uint32_t g = TK_NTT_ROOT_GENERATOR;
 #ifdef TK_NTT_ROOT_GENERATOR_ENV
         if (const char *e = getenv(TK_NTT_ROOT_GENERATOR_ENV)) {
@@ -207,49 +236,59 @@ static fr_t fr_root_top() {
             if (v >= 2 && v < 65536) g = (uint32_t)v;
         }
 #endif
-        uint32_t ex[Fr::N];   // (r - 1) >> TWO_ADICITY
-        for (int i = 0; i < Fr::N; i++) ex[i] = FrP::MOD[i];
-        ex[0] -= 1;           // r is odd: no borrow
-        const int sh = FrP::TWO_ADICITY;
-        uint32_t q[Fr::N];
-        for (int i = 0; i < Fr::N; i++) {
-            int src = i + sh / 32;
-            uint64_t lo = src < Fr::N ? ex[src] : 0, hi = src + 1 < Fr::N ? ex[src + 1] : 0;
-            q[i] = (uint32_t)(((hi << 32) | lo) >> (sh % 32));
-        }
-        fr_t base = Fr::zero();
-        base.l[0] = g;
-        base = Fr::to_mont(base);
-        fr_t acc = Fr::zero();
-        acc.l[0] = 1;
-        acc = Fr::to_mont(acc);
-        for (int bit = 32 * Fr::N - 1; bit >= 0; bit--) {
-            acc = Fr::sqr(acc);
-            if ((q[bit >> 5] >> (bit & 31)) & 1) acc = Fr::mul(acc, base);
-        }
-        return acc;
+        return root_state_t{g, fr_root_top_of(g)};
     }();
-    return top;
+    return st;
 }
-static fr_t fr_root_plain(uint32_t logn) {  // w_{2^logn}, Montgomery
-    fr_t w = fr_root_top();
+static fr_t fr_root_top() {
+    std::lock_guard<std::mutex> lk(g_dom_mu);
+    return fr_root_state().top;
+}
+static fr_t fr_root_down(fr_t w, uint32_t logn) {  // w_{2^TWO_ADICITY} -> w_{2^logn}, Montgomery
     for (uint32_t i = logn; i < (uint32_t)FrP::TWO_ADICITY; i++) w = Fr::sqr(w);
     return w;
 }
-
-TK_API tkmk_error TK_NTT_SYM_ROOT(uint64_t max_size, abi_fr *rou_out) {
+// the root of order 2^ceil(log2(max_size)) under the top root `top`; a quadratic residue as generator is refused
+static tkmk_error root_of_unity_under(const fr_t &top, uint64_t max_size, abi_fr *rou_out) {
     if (!rou_out) return TKMK_ERR_INVALID_POINTER;
     uint32_t l = 0;
     while (l < (uint32_t)FrP::TWO_ADICITY && (1ull << l) < max_size) l++;
     if ((1ull << l) < max_size) return TKMK_ERR_INVALID_ARGUMENT;
-    {   // the generator must be a quadratic non-residue: w^(2^(TWO_ADICITY-1)) = -1, not 1
-        fr_t m1 = fr_root_plain(1), one = Fr::zero();
-        one.l[0] = 1;
-        if (Fr::eq(Fr::from_mont(m1), one)) return TKMK_ERR_INVALID_ARGUMENT;
-    }
-    fr_to_api(rou_out, Fr::from_mont(fr_root_plain(l)));
+    // the generator must be a quadratic non-residue: w^(2^(TWO_ADICITY-1)) = -1, not 1
+    if (Fr::eq(fr_root_down(top, 1), Fr::one())) return TKMK_ERR_INVALID_ARGUMENT;
+    fr_to_api(rou_out, Fr::from_mont(fr_root_down(top, l)));
     return TKMK_SUCCESS;
 }
+
+TK_API tkmk_error TK_NTT_SYM_ROOT(uint64_t max_size, abi_fr *rou_out) { return root_of_unity_under(fr_root_top(), max_size, rou_out); }
+
+#ifdef TK_NTT_SYM_ROOT_WITH_GENERATOR
+// the same under a NAMED generator: pure host arithmetic, no state is read or changed
+TK_API tkmk_error TK_NTT_SYM_ROOT_WITH_GENERATOR(uint32_t g, uint64_t max_size, abi_fr *rou_out) {
+    if (g < 2) return TKMK_ERR_INVALID_ARGUMENT;
+    return root_of_unity_under(fr_root_top_of(g), max_size, rou_out);
+}
+// the generator in effect: the declared constant, the environment's initial value, or the last successful set
+TK_API tkmk_error TK_NTT_SYM_GET_GENERATOR(uint32_t *g) {
+    if (!g) return TKMK_ERR_INVALID_POINTER;
+    std::lock_guard<std::mutex> lk(g_dom_mu);
+    *g = fr_root_state().g;
+    return TKMK_SUCCESS;
+}
+// Every root of unity handed out from now on derives from g.  Refused while a domain is initialised (its twiddles and Stockham tables
+// were built under the generator in effect: release first) unless g IS the generator in effect, and for a quadratic residue.
+TK_API tkmk_error TK_NTT_SYM_SET_GENERATOR(uint32_t g) {
+    if (g < 2) return TKMK_ERR_INVALID_ARGUMENT;
+    std::lock_guard<std::mutex> lk(g_dom_mu);
+    root_state_t &st = fr_root_state();
+    if (g == st.g) return TKMK_SUCCESS;
+    if (g_dom.tw) return TKMK_ERR_INVALID_ARGUMENT;
+    const fr_t top = fr_root_top_of(g);
+    if (Fr::eq(fr_root_down(top, 1), Fr::one())) return TKMK_ERR_INVALID_ARGUMENT;
+    st = root_state_t{g, top};
+    return TKMK_SUCCESS;
+}
+#endif
 
 TK_API tkmk_error TK_NTT_SYM_INIT(const abi_fr *primitive_root, const tkmk_ntt_init_domain_config *cfg) {
     if (!primitive_root) return TKMK_ERR_INVALID_POINTER;

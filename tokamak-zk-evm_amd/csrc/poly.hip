@@ -117,6 +117,42 @@ __global__ __launch_bounds__(256) void k_scale(const fr_t *__restrict__ src, fr_
     }
 }
 
+// ---- geometric grid: out[i][k] = c0 * gx^i * gy^(col0 + col_step k), written with no input array ----
+// The identity part of s0 / s1, the monomial grid of the setup and the Lagrange-coefficient grid that identifies a CRS's root of unity
+// are all of this shape.  The kernel is store-bound: a work item owns GG_RUN consecutive ROWS of one column, reaches its first element
+// by square-and-multiply over the two tables gx^(2^j), gy^(2^j) (Montgomery, staged in LDS; a wave reads one entry at a time: a
+// broadcast) and then keeps a running product by gx; consecutive lanes own consecutive columns, so every store instruction of a wave
+// writes 64 x 32 contiguous bytes of a row.  c0 stays plain: plain x Montgomery is plain, the output needs no conversion pass.
+// 0^0 = 1 (no table entry is touched for exponent 0).
+#define GG_RUN 8
+struct gg_tables_t {
+    fr_t px[32], py[32];
+};
+__global__ __launch_bounds__(256) void k_geometric_grid(gg_tables_t t, fr_t c0, uint32_t rows, uint32_t cols, uint32_t col0, uint32_t col_step,
+                                                       fr_t *__restrict__ out) {
+    __shared__ fr_t sx[32], sy[32];
+    if (threadIdx.x < 32) sx[threadIdx.x] = t.px[threadIdx.x];
+    else if (threadIdx.x < 64) sy[threadIdx.x - 32] = t.py[threadIdx.x - 32];
+    __syncthreads();
+    const uint64_t items = (((uint64_t)rows + GG_RUN - 1) / GG_RUN) * cols;
+    for (uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; q < items; q += (uint64_t)gridDim.x * blockDim.x) {
+        const uint64_t rg = q / cols;
+        const uint32_t k = (uint32_t)(q - rg * cols);
+        const uint64_t i0 = rg * GG_RUN;                                   // < 2^32 + GG_RUN
+        const uint64_t ey = (uint64_t)col0 + (uint64_t)col_step * k;       // < 2^32 (checked by the launcher)
+        fr_t acc = c0;
+        for (uint32_t j = 0; j < 32 && (i0 >> j); j++)
+            if ((i0 >> j) & 1) acc = Fr::mul(acc, sx[j]);
+        for (uint32_t j = 0; j < 32 && (ey >> j); j++)
+            if ((ey >> j) & 1) acc = Fr::mul(acc, sy[j]);
+        fr_t *o = out + i0 * cols + k;
+        for (uint32_t r = 0; r < GG_RUN && i0 + r < rows; r++, o += cols) {
+            tk_store(o, acc);
+            acc = Fr::mul(acc, sx[0]);
+        }
+    }
+}
+
 // out[i] = sum_j m[i][j] * w[j]   (one workgroup per row; w Montgomery, result plain)
 __global__ __launch_bounds__(256) void k_row_dot(const fr_t *__restrict__ m, uint32_t ys, const fr_t *__restrict__ w,
                                                 fr_t *__restrict__ out) {
@@ -424,6 +460,25 @@ TK_API tkmk_error tkmk_poly_scale_coeffs(const tkmk_fr *src_dev, uint32_t x_size
     }
     hipLaunchKernelGGL(k_scale, stream_grid((uint64_t)x_size * y_size), 256, 0, s, (const fr_t *)src_dev, (fr_t *)dst_dev, x_size, y_size,
                        px, py, 0);
+    TK_HIP(hipGetLastError());
+    return TKMK_SUCCESS;
+}
+
+// out_dev (rows x cols, fully written, canonical plain) [i][k] = c0 * gx^i * gy^(col0 + col_step k); c0, gx, gy are HOST scalars (plain).
+// No input array: where a grid of this shape was made by scaling an uploaded matrix of ones, this writes it in place.  col0 / col_step
+// give a sharded rank its COLS slice directly (local column k = global column rank + G k).  0^0 = 1.
+TK_API tkmk_error tkmk_poly_geometric_grid(uint32_t rows, uint32_t cols, const tkmk_fr *c0, const tkmk_fr *gx, const tkmk_fr *gy, uint32_t col0,
+                                           uint32_t col_step, tkmk_fr *out_dev, tkmk_stream stream) {
+    if (!c0 || !gx || !gy || !out_dev) return TKMK_ERR_INVALID_POINTER;
+    if (!rows || !cols) return TKMK_ERR_INVALID_ARGUMENT;
+    if ((uint64_t)col0 + (uint64_t)col_step * (cols - 1) >= (1ull << 32)) return TKMK_ERR_INVALID_ARGUMENT;   // exponents are 32-bit
+    TK_TRY(tk_require_device());
+    tk_stat_add(TK_STAT_POLY_ELEMENTS, (uint64_t)rows * cols);
+    gg_tables_t t;
+    t.px[0] = Fr::to_mont(fr_in(gx)), t.py[0] = Fr::to_mont(fr_in(gy));
+    for (int j = 1; j < 32; j++) t.px[j] = Fr::sqr(t.px[j - 1]), t.py[j] = Fr::sqr(t.py[j - 1]);
+    const uint64_t items = (((uint64_t)rows + GG_RUN - 1) / GG_RUN) * cols;
+    hipLaunchKernelGGL(k_geometric_grid, stream_grid(items), 256, 0, tk_stream(stream), t, fr_in(c0), rows, cols, col0, col_step, (fr_t *)out_dev);
     TK_HIP(hipGetLastError());
     return TKMK_SUCCESS;
 }

@@ -58,6 +58,8 @@ int main(int argc, char **argv) {
         size_t xy_points = 0, gamma_points = 0;
         CrsPayload crs;
         std::shared_ptr<void> keep;
+        bool have_kl = false;   // lagrange_KL comes with the combined reference string only
+        G1Affine lagrange_KL{};
         const std::string pre_archive = crs_dir + "/sigma_preprocess.rkyv";
         if (!file_exists(crs_dir + "/combined_sigma.tkcrs") && file_exists(pre_archive)) {
             auto m = map_file(pre_archive);
@@ -65,10 +67,15 @@ int main(int argc, char **argv) {
             rkyv::PreprocessSigma ps = rkyv::decode_sigma_preprocess(m.first.data(), m.first.size());
             xy_host = reinterpret_cast<const G1Affine *>(ps.xy_powers), xy_points = ps.xy_points;
             gamma_host = reinterpret_cast<const G1Affine *>(ps.gamma_inv_o_inst), gamma_points = ps.gamma_points;
+            if (file_exists(crs_dir + "/combined_sigma.rkyv")) {   // the archive next to it carries the record the root-of-unity check needs
+                CrsPayload whole = load_combined_sigma(crs_dir, sp);
+                lagrange_KL = whole.g1(CrsPayload::G1Singles)[5], have_kl = true;
+            }
         } else {
             crs = load_combined_sigma(crs_dir, sp);
             xy_host = crs.g1(CrsPayload::XyPowers), xy_points = crs.points(CrsPayload::XyPowers);
             gamma_host = crs.g1(CrsPayload::GammaInvOInst), gamma_points = crs.points(CrsPayload::GammaInvOInst);
+            lagrange_KL = crs.g1(CrsPayload::G1Singles)[5], have_kl = true;
         }
         if (xy_points != rs_x * rs_y || gamma_points != sp.l) throw Error("CRS sections do not match setupParams.json");
         std::vector<Permutation> perm;
@@ -78,7 +85,15 @@ int main(int argc, char **argv) {
         std::vector<ScalarField> a_fn;
         const json::Value jinst = json::read_file(synth_dir + "/instance.json");
         for (const json::Value &e : jinst.at("a_pub_function").items()) a_fn.push_back(fr_from_hex(e.as_string()));
-        Sigma1 sigma(DeviceVec<G1Affine>::from_host(xy_host, xy_points), rs_x, rs_y);
+        // s0, s1 and O_pub_fix depend on omega but not on lagrange_KL: the generator the reference string was made under is adopted
+        // exactly as the prover adopts it (identify_crs_root, host/tkmk_prover.hpp), before anything that depends on omega exists; a
+        // string whose lagrange_KL follows under no candidate is a warning here, not a refusal
+        DeviceVec<G1Affine> xy_dev = DeviceVec<G1Affine>::from_host(xy_host, xy_points);
+        if (have_kl) {
+            const CrsRootVerdict v = identify_crs_root(xy_dev.ptr(), TKMK_BASES_PLAIN, lagrange_KL, sp, false);
+            if (v.switched) fprintf(stderr, "preprocess: the reference string was made under root-of-unity generator %u: adopted for this run\n", v.generator);
+        }
+        Sigma1 sigma(std::move(xy_dev), rs_x, rs_y);
         DeviceVec<G1Affine> gamma = DeviceVec<G1Affine>::from_host(gamma_host, gamma_points);
         Preprocess pre = Preprocess::gen(sigma, gamma, perm, a_fn, sp);
         std::string path = out_dir + "/preprocess.json";

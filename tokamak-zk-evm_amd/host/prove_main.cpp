@@ -66,7 +66,8 @@ int main(int argc, char **argv) {
         check(tkmk_free(warm), "free");
         double t_dev = Prover::now();
         printf("Prover initialization...\n");
-        auto ctx = ProverContext::open(lib_dir, crs_dir, [&](const SetupParams &sp, std::string &source) { return load_prover_sigma(crs_dir, sp, source); });
+        auto ctx = ProverContext::open(lib_dir, crs_dir, [&](const SetupParams &sp, std::string &source, const CrsGridHook &hook) { return load_prover_sigma(crs_dir, sp, source, 0, Shard{}, nullptr, hook); });
+        if (ctx->root_adopted) fprintf(stderr, "prove: the reference string was made under root-of-unity generator %u: adopted for this run\n", ctx->root_generator);
         double t_open = Prover::now();
         Mixer mixer;
 #ifdef TKMK_TESTING_MODE

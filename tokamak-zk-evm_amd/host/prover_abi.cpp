@@ -54,7 +54,7 @@ TKP_API tkmk_error tkmk_prover_open(const char *subcircuit_library_dir, const ch
         std::string crs = crs_dir;
         DefaultStreamTurn turn(false);
         std::unique_ptr<tkmk_prover> p(new tkmk_prover());
-        p->ctx = ProverContext::open(subcircuit_library_dir, crs, [&](const SetupParams &sp, std::string &source) { return load_prover_sigma(crs, sp, source, resident_table_c(sp)); });
+        p->ctx = ProverContext::open(subcircuit_library_dir, crs, [&](const SetupParams &sp, std::string &source, const CrsGridHook &hook) { return load_prover_sigma(crs, sp, source, resident_table_c(sp), Shard{}, nullptr, hook); });
         *out = p.release();
     });
 }
@@ -114,7 +114,7 @@ TKP_API tkmk_error tkmk_prover_open_sharded(void *comm, const char *subcircuit_l
         std::string crs = crs_dir;
         std::unique_ptr<tkmk_prover> p(new tkmk_prover());
         p->ctx = ProverContext::open(
-            subcircuit_library_dir, crs, [&](const SetupParams &sp, std::string &source) { return load_prover_sigma(crs, sp, source, resident_table_c(sp, link.shard.world), link.shard); }, link);
+            subcircuit_library_dir, crs, [&](const SetupParams &sp, std::string &source, const CrsGridHook &hook) { return load_prover_sigma(crs, sp, source, resident_table_c(sp, link.shard.world), link.shard, nullptr, hook); }, link);
         *out = p.release();
     });
 }
@@ -173,3 +173,4 @@ TKP_API tkmk_error tkmk_prover_close(tkmk_prover *p) {
 TKP_API void tkmk_prover_free_string(char *s) { std::free(s); }
 TKP_API const char *tkmk_prover_last_error(void) { return g_last_error.c_str(); }
 TKP_API const char *tkmk_prover_crs_source(const tkmk_prover *p) { return p ? p->ctx->crs_source.c_str() : ""; }
+TKP_API uint32_t tkmk_prover_root_generator(const tkmk_prover *p) { return p ? p->ctx->root_generator : 0; }

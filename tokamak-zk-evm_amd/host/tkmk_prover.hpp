@@ -6,12 +6,14 @@
 // prove2's p_comb is one pass of the fused expression evaluator.
 #pragma once
 #include <array>
+#include <atomic>
 #include <chrono>
 #include <functional>
 #include <future>
 #include <initializer_list>
 #include <map>
 #include <memory>
+#include <mutex>
 #include <sys/random.h>
 
 #include <cerrno>
@@ -119,6 +121,106 @@ struct Proof {
     std::string to_json() const { return entries_json("proof_entries_part1", "proof_entries_part2", convert_format_for_solidity_verifier()); }
 };
 
+// ---- which root of unity was this CRS made under?  (include/tkmk.h: TKMK_BLS12_381_FR_ROOT_GENERATOR, tkmk_crs_identify_root) ----
+// The generator of the scalar field's two-adic subgroup is the one convention of the path the reference does not pin (it comes from
+// ICICLE).  The CRS itself says which one it was made under: lagrange_KL follows from xy_powers under exactly one of them.  So the
+// prover and `preprocess` ask, right after the table is resident and BEFORE anything that depends on omega exists (NTT domain, the
+// identity part of s0 / s1, the Lagrange tables): one MSM per candidate over the m_I x s_max corner.
+//   candidates   TKMK_FR_ROOT_GENERATOR set: that value alone (the operator pinned it); otherwise the generator in effect, then the other(s)
+//                of {5, 7}
+//   exactly one matches and it is not the generator in effect: the NTT domain is released and the generator replaced, process-wide —
+//                unless another prover context of the process is open (it was built under the generator in effect): refused
+//   several match (m_I <= 2 and s_max <= 2: both roots are -1): the generator in effect stays
+//   none matches: `enforce` (the prover) throws TKMK_ERR_INVALID_ARGUMENT naming every generator tried; otherwise (`preprocess`, whose
+//                output depends on omega but not on lagrange_KL) a warning on stderr and the generator in effect stays
+// Sharded (dist_ctx() installed): `grid` is still the WHOLE table on every rank; a rank sums its columns rank + G k only, ONE all-gather
+// carries the partials, every rank adds them and so reaches the same decision — a refusal is every rank's refusal.
+inline std::atomic<int> &open_prover_contexts() {
+    static std::atomic<int> n{0};
+    return n;
+}
+struct CrsRootVerdict {
+    uint32_t generator = 0;    // the generator the process runs under from here on
+    bool switched = false;     // it was adopted from the CRS (it differs from what was in effect before)
+    bool matched = true;       // false: no candidate reproduced lagrange_KL (only returned when !enforce)
+};
+inline CrsRootVerdict identify_crs_root(const G1Affine *grid_dev, int bases_form, const G1Affine &lagrange_KL, const SetupParams &sp, bool enforce) {
+    const size_t m_i = sp.l_D - sp.l, rs_x = std::max(2 * sp.n, 2 * m_i), rs_y = 2 * sp.s_max;
+    uint32_t in_effect = 0;
+    check(tkmk_ntt_root_generator(&in_effect), "tkmk_ntt_root_generator");
+    std::vector<uint32_t> cand;
+    bool pinned = false;
+    if (const char *e = std::getenv("TKMK_FR_ROOT_GENERATOR")) {
+        const int v = std::atoi(e);
+        if (v >= 2 && v < 65536) pinned = true, cand.push_back((uint32_t)v);
+    }
+    if (!pinned) {
+        cand.push_back(in_effect);
+        for (uint32_t g : {5u, 7u})
+            if (g != in_effect) cand.push_back(g);
+    }
+    std::string tried;
+    for (uint32_t g : cand) tried += (tried.empty() ? "" : ", ") + std::to_string(g);
+    host_trace("identify_crs_root: candidates %s over the %zu x %zu corner", tried.c_str(), m_i, (size_t)sp.s_max);
+    const DistCtx &dc = dist_ctx();
+    const size_t C = cand.size(), G = dc.on() ? dc.G() : 1;
+    std::vector<tkmk_g1_projective> mine(C);
+    check(tkmk_crs_identify_root(grid_dev, bases_form, (uint32_t)rs_x, (uint32_t)rs_y, (uint32_t)m_i, (uint32_t)sp.s_max, dc.on() ? dc.r() : 0u, (uint32_t)G,
+                                 cand.data(), (int)C, mine.data()),
+          "tkmk_crs_identify_root");
+    auto affine_of = [](const tkmk_g1_projective &res) {   // canonical (x, y, 1) / (0, 1, 0): dropping z is G1Affine::from(projective)
+        G1Affine out{};
+        bool inf = true;
+        for (uint32_t l : res.z.limbs) inf &= l == 0;
+        if (!inf) out.x = res.x, out.y = res.y;
+        return out;
+    };
+    std::vector<G1Affine> sums(C);
+    for (size_t c = 0; c < C; c++) sums[c] = affine_of(mine[c]);
+    if (G > 1) {   // rank-major partials of every rank -> per candidate the sum over the ranks (a host-operand MSM batch of G unit terms each)
+        std::vector<G1Affine> all(C * G), pts(C * G);
+        check(dc.all_gather_host(dc.comm, sums.data(), C * sizeof(G1Affine), all.data()), "tkmk_comm_all_gather_host");
+        for (size_t c = 0; c < C; c++)
+            for (size_t r = 0; r < G; r++) pts[c * G + r] = all[r * C + c];
+        std::vector<ScalarField> ones(C * G, fr_from_u32(1));
+        tkmk_msm_config hc = tkmk_msm_default_config();
+        hc.batch_size = (int)C, hc.are_points_shared_in_batch = false;
+        std::vector<tkmk_g1_projective> res(C);
+        check(bls12_381_msm(ones.data(), pts.data(), (int)G, &hc, res.data()), "sum of the ranks' partials");
+        for (size_t c = 0; c < C; c++) sums[c] = affine_of(res[c]);
+    }
+    std::vector<uint32_t> match;
+    for (size_t c = 0; c < C; c++)
+        if (std::memcmp(&sums[c], &lagrange_KL, sizeof(G1Affine)) == 0) match.push_back(cand[c]);
+    CrsRootVerdict v;
+    v.generator = in_effect;
+    if (match.empty()) {
+        const std::string msg = "the reference string's lagrange_KL does not follow from its xy_powers under any root-of-unity generator tried (" + tried +
+                                (pinned ? "; pinned by TKMK_FR_ROOT_GENERATOR" : "") + ")";
+        if (enforce) throw Error(msg + ": the CRS is damaged or was made under another convention");
+        fprintf(stderr, "warning: %s; going on under generator %u\n", msg.c_str(), in_effect);
+        v.matched = false;
+        return v;
+    }
+    for (uint32_t g : match)
+        if (g == in_effect) return v;   // the generator in effect reproduces it (alone, or with the others when both roots are -1)
+    const uint32_t want = match[0];
+    static std::mutex switch_mu;         // the ranks of a loopback communicator are threads of one process: one of them switches
+    std::lock_guard<std::mutex> lk(switch_mu);
+    check(tkmk_ntt_root_generator(&in_effect), "tkmk_ntt_root_generator");
+    if (in_effect != want) {
+        if (open_prover_contexts().load() > 0)
+            throw Error("this reference string was made under root-of-unity generator " + std::to_string(want) + ", but another prover context of this process is open under generator " +
+                                                       std::to_string(in_effect) + ": the generator is process-wide; close that context first, or use one process per convention");
+        check(bls12_381_ntt_release_domain(), "ntt::release_domain");
+        check(tkmk_ntt_set_root_generator(want), "tkmk_ntt_set_root_generator");
+    }
+    host_trace("identify_crs_root: the CRS was made under generator %u: adopted", want);
+    v.generator = want, v.switched = true;
+    return v;
+}
+using CrsGridHook = std::function<void(const G1Affine *grid_dev, const G1Affine &lagrange_KL)>;   // the whole table, plain records, just uploaded
+
 // the CRS parts `prove` uses (SigmaHolder::load of combined_sigma: libs/src/group_structures/mod.rs:313-551 for the names)
 struct ProverSigma {
     Sigma1 sigma1;
@@ -138,7 +240,7 @@ struct ProverSigma {
     // are sharded the same way; the caller drops it afterwards.  The binding tables are replicated (every rank commits the index lists
     // of its own placements).
     static ProverSigma from_payload(const CrsPayload &crs, const SetupParams &sp, uint32_t table_c = 0, Shard shard = Shard{},
-                                    std::unique_ptr<Sigma1> *whole_grid = nullptr) {
+                                    std::unique_ptr<Sigma1> *whole_grid = nullptr, const CrsGridHook &on_grid = CrsGridHook()) {
         size_t m_i = sp.l_D - sp.l, rs_x = std::max(2 * sp.n, 2 * m_i), rs_y = 2 * sp.s_max;
         auto want = [&](CrsPayload::Section s, size_t pts, const char *name) {
             if (crs.points(s) != pts) throw Error(std::string("CRS section ") + name + " does not match setupParams.json");
@@ -163,6 +265,7 @@ struct ProverSigma {
                     if (base + k < rs_y) edge[{0, base + k}] = xy[base + k];
         }
         DeviceVec<G1Affine> grid = crs.upload(CrsPayload::XyPowers);
+        if (on_grid) on_grid(grid.ptr(), singles[5]);   // before the table is cut into columns, converted and expanded
         DeviceVec<G1Affine> mine = shard.world > 1 ? Sigma1::cols_of_grid(grid, rs_x, rs_y, shard) : DeviceVec<G1Affine>();
         if (shard.world > 1 && whole_grid) whole_grid->reset(new Sigma1(std::move(grid), rs_x, rs_y, 0));
         ProverSigma out{Sigma1(shard.world > 1 ? std::move(mine) : std::move(grid), rs_x, rs_y, table_c, shard),

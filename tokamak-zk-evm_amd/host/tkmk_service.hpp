@@ -96,6 +96,8 @@ class ProverContext {
     unsigned threads = 1;
     std::unique_ptr<ProverSigma> sigma;   // tables in the MSM's resident form (see open)
     std::string crs_source;               // which container the CRS came from
+    uint32_t root_generator = 0;          // the root-of-unity generator this context runs under (identified from the CRS at open)
+    bool root_adopted = false;            // ... and it was adopted from the CRS: it is not what the process started with
     ShardLink link;                       // set: this context is rank link.shard.rank of a sharded prover
 
   private:
@@ -118,6 +120,7 @@ class ProverContext {
     ScalarField *pinned_ = nullptr;                                 // witness staging
     uint64_t pinned_cap_ = 0;
     std::vector<uint32_t> n_wires_;
+    bool counted_ = false;                                          // this context is in open_prover_contexts()
 
     static WireLists make_lists(const std::vector<std::vector<std::pair<uint32_t, uint32_t>>> &per_kind) {
         WireLists L;
@@ -147,6 +150,7 @@ class ProverContext {
     ProverContext(const ProverContext &) = delete;
     ProverContext &operator=(const ProverContext &) = delete;
     ~ProverContext() {
+        if (counted_) open_prover_contexts()--;
         if (lib_) tkmk_r1cs_library_destroy(lib_);
         if (pinned_) tkmk_host_free(pinned_);
         if (binding_stream_) tkmk_stream_destroy(binding_stream_);
@@ -164,8 +168,11 @@ class ProverContext {
     // combined_sigma.tkcrs payload when only that is present)
     // link set: load_sigma returns this rank's columns of xy_powers; everything derived from them (table expansion, the Lagrange-basis
     // tables and their prefix sums) is made from those columns, 1 / G of the work per rank
+    // load_sigma hands its third argument to ProverSigma::from_payload: the hook that identifies the root of unity the CRS was made under
+    // (identify_crs_root, host/tkmk_prover.hpp) while the uploaded table is still whole and plain.  Nothing that depends on omega — the NTT
+    // domain, the identity part of s0 / s1, the Lagrange tables — exists before it has run.
     static std::unique_ptr<ProverContext> open(const std::string &lib_dir, const std::string &crs_dir,
-                                               const std::function<std::unique_ptr<ProverSigma>(const SetupParams &, std::string &)> &load_sigma,
+                                               const std::function<std::unique_ptr<ProverSigma>(const SetupParams &, std::string &, const CrsGridHook &)> &load_sigma,
                                                const ShardLink &link = ShardLink{}) {
         std::unique_ptr<ProverContext> c(new ProverContext());
         c->link = link;
@@ -198,8 +205,6 @@ class ProverContext {
                 c->n_consts.push_back(e.at("Nconsts").as_size());
             }
         }
-        init_ntt_domain_for_size(4 * std::max(c->m_i, sp.n) * 2 * sp.s_max);   // prover_verifier_ntt_domain_size (libs/src/utils/mod.rs:51-58)
-
         // constraint library -> device CSR, and the static wire lists
         const size_t K = c->infos.size();
         std::vector<SubcircuitR1CS> r1cs(K);
@@ -234,6 +239,16 @@ class ProverContext {
         c->n_wires_ = n_wires;
         c->iface_ = make_lists(iface), c->prv_ = make_lists(prv), c->pub_ = make_lists(pub);
 
+        host_trace("open: loading the CRS");
+        bool identified = false;
+        c->sigma = load_sigma(sp, c->crs_source, [&](const G1Affine *grid_dev, const G1Affine &lagrange_KL) {
+            const CrsRootVerdict v = identify_crs_root(grid_dev, TKMK_BASES_PLAIN, lagrange_KL, sp, true);
+            c->root_generator = v.generator, c->root_adopted = v.switched, identified = true;
+        });
+        if (!identified) throw Error("ProverContext::open: the CRS loader did not run the root-of-unity check");
+        host_trace("open: CRS resident (root-of-unity generator %u%s)", c->root_generator, c->root_adopted ? ", adopted from the CRS" : "");
+        init_ntt_domain_for_size(4 * std::max(c->m_i, sp.n) * 2 * sp.s_max);   // prover_verifier_ntt_domain_size (libs/src/utils/mod.rs:51-58)
+
         // Permutation::to_poly's identity part (libs/src/iotools/mod.rs:419-437): s0[row][col] = w_x^row, s1[row][col] = w_y^col — this rank's
         // columns of them (COLS layout: local column k is column rank + G k; all columns on one GPU)
         {
@@ -261,9 +276,6 @@ class ProverContext {
             c->xp_ = DeviceVec<ScalarField>::from_host(xp), c->yp_ = DeviceVec<ScalarField>::from_host(yp);
         }
 
-        host_trace("open: loading the CRS");
-        c->sigma = load_sigma(sp, c->crs_source);
-        host_trace("open: CRS resident");
         // binding tables -> resident form, in place (Sigma1 converts xy_powers itself)
         tkmk_msm_config cfg = tkmk_msm_default_config();
         cfg.are_points_on_device = cfg.are_results_on_device = true;
@@ -381,6 +393,7 @@ class ProverContext {
         check(tkmk_device_synchronize(), "synchronize");
         check(tkmk_release_scratch(), "release_scratch");   // the one-time transforms' scratch (1.6 GB for the group NTT) is not a proof's
         check(tkmk_device_synchronize(), "synchronize");
+        open_prover_contexts()++, c->counted_ = true;
         return c;
     }
 

@@ -100,6 +100,7 @@ SYMBOLS = [
     "tkmk_msm_multi_ex", "bls12_381_msm_convert_bases", "tkmk_r1cs_library_create", "tkmk_r1cs_library_destroy", "tkmk_r1cs_library_eval",
     "tkmk_witness_route", "tkmk_fr_scatter_table", "tkmk_msm_set_pipeline_streams", "tkmk_msm_get_pipeline_streams", "tkmk_host_malloc", "tkmk_host_free", "tkmk_stats_reset", "tkmk_stats_get",
     "bls12_381_ntt_domain_size", "bn254_ntt_domain_size", "tkmk_poly_lincomb", "tkmk_bintt_padded", "tkmk_diag_device_switch", "tkmk_diag_gather_probe",
+    "bls12_381_get_root_of_unity_with_generator", "tkmk_ntt_root_generator", "tkmk_ntt_set_root_generator", "tkmk_poly_geometric_grid", "tkmk_crs_identify_root",
     "bls12_381_generate_random_affine_points", "bls12_381_generate_scalars", "bls12_381_polynomial_add", "bls12_381_polynomial_clone", "bls12_381_polynomial_coeffs_device_ptr", "bls12_381_polynomial_copy_coeffs", "bls12_381_polynomial_create_from_coefficients", "bls12_381_polynomial_create_from_rou_evaluations", "bls12_381_polynomial_degree", "bls12_381_polynomial_delete", "bls12_381_polynomial_divide", "bls12_381_polynomial_evaluate", "bls12_381_polynomial_get_coeff", "bls12_381_polynomial_multiply", "bls12_381_polynomial_multiply_by_scalar", "bls12_381_polynomial_nof_coeffs", "bls12_381_polynomial_slice", "bls12_381_polynomial_subtract", "bls12_381_vector_accumulate",
 ]
 
@@ -215,6 +216,25 @@ def get_root_of_unity(max_size, curve="bls12_381"):
     out = np.empty(32, np.uint8)
     _check(getattr(lib(), sym)(ctypes.c_uint64(max_size), _p(out)), sym)
     return out
+
+
+def get_root_of_unity_with_generator(g, max_size):
+    """the root bls12_381_get_root_of_unity would give if omega_{2^32} were g^((r-1)/2^32): host arithmetic, no state (BLS12-381 only)"""
+    out = np.empty(32, np.uint8)
+    _check(lib().bls12_381_get_root_of_unity_with_generator(ctypes.c_uint32(g), ctypes.c_uint64(max_size), _p(out)), "bls12_381_get_root_of_unity_with_generator")
+    return out
+
+
+def root_generator():
+    """the generator get_root_of_unity derives from at this moment (tkmk_ntt_root_generator)"""
+    g = ctypes.c_uint32()
+    _check(lib().tkmk_ntt_root_generator(ctypes.byref(g)), "tkmk_ntt_root_generator")
+    return g.value
+
+
+def set_root_generator(g):
+    """replaces it process-wide; refused (TkmkError, code 11) while an NTT domain is initialised and for a quadratic residue"""
+    _check(lib().tkmk_ntt_set_root_generator(ctypes.c_uint32(g)), "tkmk_ntt_set_root_generator")
 
 
 _domain_size = {}
@@ -584,6 +604,26 @@ def msm_multi_ex(jobs, bases_form=BASES_PLAIN, c=0, bitsize=0, stream=None):
     arr = msm_job_ex_array(jobs)
     out = np.empty(144 * len(jobs), np.uint8)
     _check(lib().tkmk_msm_multi_ex(arr, len(jobs), ctypes.byref(cfg), int(bases_form), _p(out)), "tkmk_msm_multi_ex")
+    return out
+
+
+def poly_geometric_grid(rows, cols, c0, gx, gy, col0=0, col_step=1, out=None, stream=None):
+    """tkmk_poly_geometric_grid: DeviceBuffer of rows x cols scalars, [i][k] = c0 * gx^i * gy^(col0 + col_step k) (0^0 = 1), written
+    with no input array; c0, gx, gy are 32-byte host scalars"""
+    out = DeviceBuffer(32 * rows * cols) if out is None else out
+    _check(lib().tkmk_poly_geometric_grid(ctypes.c_uint32(rows), ctypes.c_uint32(cols), _p(c0), _p(gx), _p(gy), ctypes.c_uint32(col0), ctypes.c_uint32(col_step),
+                                          _p(out), stream), "tkmk_poly_geometric_grid")
+    return out
+
+
+def crs_identify_root(xy_powers, h_max, rs_y, m_i, s_max, candidates, bases_form=BASES_PLAIN, col0=0, col_step=1):
+    """tkmk_crs_identify_root: for every candidate generator the sum that equals the CRS's lagrange_KL if the CRS was made under it, over
+    the columns col0 + col_step k < s_max of the m_i x s_max corner of xy_powers (DeviceBuffer, h_max x rs_y records in bases_form)
+    -> 144 * len(candidates) bytes of projective results on the host; the caller adds partials and compares"""
+    cand = (ctypes.c_uint32 * len(candidates))(*[int(g) for g in candidates])
+    out = np.empty(144 * len(candidates), np.uint8)
+    _check(lib().tkmk_crs_identify_root(_p(xy_powers), int(bases_form), ctypes.c_uint32(h_max), ctypes.c_uint32(rs_y), ctypes.c_uint32(m_i), ctypes.c_uint32(s_max),
+                                        ctypes.c_uint32(col0), ctypes.c_uint32(col_step), cand, len(candidates), _p(out)), "tkmk_crs_identify_root")
     return out
 
 

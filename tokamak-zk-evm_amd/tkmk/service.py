@@ -18,7 +18,7 @@ TEST_PARTS, COEFFICIENT_BASIS = 1, 2        # TKMK_PROVE_* of include/tkmk_prove
 
 # every symbol include/tkmk_prover.h declares (tests/test_abi.py checks the library exports all of them)
 SYMBOLS = ["tkmk_prover_open", "tkmk_prover_open_sharded", "tkmk_prover_world_size", "tkmk_prover_prove", "tkmk_prover_prove_ex", "tkmk_prover_close", "tkmk_prover_free_string", "tkmk_prover_last_error",
-           "tkmk_prover_crs_source"]
+           "tkmk_prover_crs_source", "tkmk_prover_root_generator"]
 
 
 class ProveTiming(ctypes.Structure):
@@ -42,6 +42,8 @@ def lib(testing=False):
         l.tkmk_prover_last_error.restype = ctypes.c_char_p
         l.tkmk_prover_crs_source.restype = ctypes.c_char_p
         l.tkmk_prover_crs_source.argtypes = [ctypes.c_void_p]
+        l.tkmk_prover_root_generator.restype = ctypes.c_uint32
+        l.tkmk_prover_root_generator.argtypes = [ctypes.c_void_p]
         l.tkmk_prover_free_string.argtypes = [ctypes.c_void_p]
         l.tkmk_prover_close.argtypes = [ctypes.c_void_p]
         _libs[path] = l
@@ -77,6 +79,11 @@ class Prover:
     @property
     def crs_source(self):
         return self._lib.tkmk_prover_crs_source(self._h).decode()
+
+    @property
+    def root_generator(self):
+        """the root-of-unity generator the context runs under: identified from the CRS at open (include/tkmk_prover.h)"""
+        return int(self._lib.tkmk_prover_root_generator(self._h))
 
     def prove(self, synthesizer_dir, output_dir=None, testing_mixer_json=None, want_json=True, test_parts=False, coefficient_basis=False,
               want_boxes=False):
