@@ -104,6 +104,33 @@ const char *tkmk_prover_crs_source(const tkmk_prover *p);
 /* the root-of-unity generator the context runs under: the one its reference string was made under (see tkmk_prover_open) */
 uint32_t tkmk_prover_root_generator(const tkmk_prover *p);
 
+/* ---- The verifier (verify-rust/src/lib.rs: Verifier::init + verify_snark; host/tkmk_verify.hpp, host/tkmk_pairing.hpp) ----
+ * HOST ONLY: none of the three calls below touches a device, so they also work where there is none; a verification is ~25 G1 scalar
+ * multiplications, one ten-pair Miller loop and one final exponentiation, plus the membership checks of 26 G1 and 10 G2 points: about
+ * 0.1 s on one core.
+ *
+ * *is_one = 1 iff prod_i e(p[i], q[i]) = 1 for BLS12-381 (n = 0: 1; a pair with the all-zero record = infinity on either side
+ * contributes 1).  Every point is checked first: a coordinate >= p, a point off its curve or outside the subgroup of order r gives
+ * TKMK_ERR_INVALID_ARGUMENT, and tkmk_prover_last_error() names the index and the reason. */
+tkmk_error tkmk_pairing_product_is_one(const tkmk_g1_affine *p, const tkmk_g2_affine *q, size_t n, int *is_one);
+/* What the reference's `verify` does with the same five directories: reads <lib>/setupParams.json, <synthesizer>/instance.json,
+ * <crs>/sigma_verify.json, <preprocess>/preprocess.json, <proof>/proof.json, replays the transcript, draws kappa2 from getrandom() and
+ * decides the ten-pairing equation.  *ok = 1 / 0 is the decision, with TKMK_SUCCESS either way: 0 also for a well-formed document that
+ * holds an invalid group element (off the curve, outside the subgroup, coordinate >= p) or an all-zero Sigma2.  A document that cannot
+ * be read or parsed is an error (the message names the file).
+ * root_generator: the generator g (omega_{2^32} = g^((r-1)/2^32)) the reference string was made under; 0 = the one in effect:
+ * TKMK_FR_ROOT_GENERATOR, else TKMK_BLS12_381_FR_ROOT_GENERATOR.  sigma_verify.json cannot tell which it was, so exactly this one is
+ * used and no other is tried.  report_json_out (optional, tkmk_prover_free_string): {"generator", "ok", "reason", "thetas": [3], "kappa0",
+ * "chi", "zeta", "kappa1", "a_eval"} — scalars as 0x + 64 hex digits; the challenges are absent when the decision fell before them. */
+tkmk_error tkmk_verify_files(const char *subcircuit_library_dir, const char *crs_dir, const char *synthesizer_dir, const char *preprocess_dir,
+                             const char *proof_dir, uint32_t root_generator, int *ok, char **report_json_out);
+/* The self-check of a resident context: the same decision with G, x, y, lagrange_KL and Sigma2 taken from the context's own reference
+ * string (the G1Singles and G2Points sections it was opened with) and the generator the context runs under
+ * (tkmk_prover_root_generator) — a context that adopted generator 7 at open verifies its own proofs with no environment set.  Pure host
+ * work on host copies: no device call, no change to the proving state, no collective — every rank of a sharded context may call it. */
+tkmk_error tkmk_prover_verify(tkmk_prover *p, const char *synthesizer_dir, const char *preprocess_dir, const char *proof_dir, int *ok,
+                              char **report_json_out);
+
 #ifdef __cplusplus
 }
 #endif

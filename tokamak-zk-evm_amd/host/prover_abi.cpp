@@ -1,6 +1,7 @@
 // prover_abi.cpp — libtkmk_prover.so: the C ABI of include/tkmk_prover.h over host/tkmk_service.hpp (ProverContext).
 // Built twice: libtkmk_prover.so (production: blinding scalars always from getrandom(), a testing_mixer_json argument is refused)
 // and, with -DTKMK_TESTING_MODE, libtkmk_prover_testing.so for the differential tests (the reference's `testing-mode` feature).
+// Both carry the verifier's three entries (host/tkmk_verify.hpp, host/tkmk_pairing.hpp): pure host work, no device call.
 #include <dlfcn.h>
 
 #include <cstdlib>
@@ -11,6 +12,7 @@
 #include "../../include/tkmk_prover.h"
 #include "tkmk_crs_load.hpp"
 #include "tkmk_service.hpp"
+#include "tkmk_verify.hpp"
 
 using namespace tkmk;
 
@@ -174,3 +176,60 @@ TKP_API void tkmk_prover_free_string(char *s) { std::free(s); }
 TKP_API const char *tkmk_prover_last_error(void) { return g_last_error.c_str(); }
 TKP_API const char *tkmk_prover_crs_source(const tkmk_prover *p) { return p ? p->ctx->crs_source.c_str() : ""; }
 TKP_API uint32_t tkmk_prover_root_generator(const tkmk_prover *p) { return p ? p->ctx->root_generator : 0; }
+
+// ---- the verifier (host only: none of these touches the device, the default stream or a context's proving state) ----
+static void hand_over(bool verdict, const verify::Report &rep, int *ok, char **report_json_out) {
+    if (report_json_out) *report_json_out = dup_string(rep.to_json());
+    *ok = verdict ? 1 : 0;
+}
+
+TKP_API tkmk_error tkmk_pairing_product_is_one(const tkmk_g1_affine *p, const tkmk_g2_affine *q, size_t n, int *is_one) {
+    if (!is_one || (n && (!p || !q))) return TKMK_ERR_INVALID_POINTER;
+    *is_one = 0;
+    return guarded([&] {
+        std::vector<pairing::Pair> pairs(n);
+        for (size_t i = 0; i < n; i++) {
+            const char *why = pairing::g1_check(p[i], pairs[i].p);
+            if (*why) throw Error("tkmk_pairing_product_is_one: G1 point " + std::to_string(i) + " " + why);
+            why = pairing::g2_check(reinterpret_cast<const uint8_t *>(&q[i]), pairs[i].q);
+            if (*why) throw Error("tkmk_pairing_product_is_one: G2 point " + std::to_string(i) + " " + why);
+        }
+        *is_one = pairing::product_is_one(pairs) ? 1 : 0;
+    });
+}
+
+TKP_API tkmk_error tkmk_verify_files(const char *subcircuit_library_dir, const char *crs_dir, const char *synthesizer_dir, const char *preprocess_dir,
+                                     const char *proof_dir, uint32_t root_generator, int *ok, char **report_json_out) {
+    if (!subcircuit_library_dir || !crs_dir || !synthesizer_dir || !preprocess_dir || !proof_dir || !ok) return TKMK_ERR_INVALID_POINTER;
+    *ok = 0;
+    if (report_json_out) *report_json_out = nullptr;
+    return guarded([&] {
+        verify::Report rep;
+        const bool verdict = verify::verify_files(subcircuit_library_dir, crs_dir, synthesizer_dir, preprocess_dir, proof_dir, root_generator, rep);
+        hand_over(verdict, rep, ok, report_json_out);
+    });
+}
+
+TKP_API tkmk_error tkmk_prover_verify(tkmk_prover *p, const char *synthesizer_dir, const char *preprocess_dir, const char *proof_dir, int *ok,
+                                      char **report_json_out) {
+    if (!p || !synthesizer_dir || !preprocess_dir || !proof_dir || !ok) return TKMK_ERR_INVALID_POINTER;
+    *ok = 0;
+    if (report_json_out) *report_json_out = nullptr;
+    return guarded([&] {
+        const ProverContext &c = *p->ctx;
+        verify::Inputs in;
+        in.sp.n = c.sp.n, in.sp.l = c.sp.l, in.sp.l_D = c.sp.l_D, in.sp.s_max = c.sp.s_max, in.sp.l_user = c.sp.l_user, in.sp.l_free = c.sp.l_free;
+        verify::validate_shape(in.sp);
+        in.a_pub = verify::read_instance(synthesizer_dir, in.sp);
+        verify::read_preprocess(preprocess_dir, in);
+        verify::read_proof(proof_dir, in);
+        // the reference string is the context's own: G, x, y, lagrange_KL of the G1Singles section and Sigma2 of the G2Points section
+        const auto &s = c.sigma->g1_singles;
+        in.pt[verify::CRS_G] = s[0], in.pt[verify::CRS_X] = s[1], in.pt[verify::CRS_Y] = s[2], in.pt[verify::CRS_KL] = s[5];
+        for (int k = 0; k < verify::G2Count; k++) std::memcpy(in.g2[k].data(), c.sigma->g2_points.data() + 192 * k, 192);
+        in.crs_label = c.crs_source;
+        verify::Report rep;
+        const bool verdict = verify::verify_loaded(in, c.root_generator, rep);   // the generator the context identified at open
+        hand_over(verdict, rep, ok, report_json_out);
+    });
+}

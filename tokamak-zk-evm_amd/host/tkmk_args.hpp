@@ -22,7 +22,7 @@
 #include <string>
 #include <vector>
 
-#include "tkmk_host.hpp"
+#include "tkmk_base.hpp"
 
 namespace tkmk {
 namespace args {

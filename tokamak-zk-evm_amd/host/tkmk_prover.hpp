@@ -230,6 +230,10 @@ struct ProverSigma {
     bool binding_tables_converted = false;   // ProverContext keeps the three binding tables in the MSM's resident form
     // host copies of the few xy_powers entries the blinding terms of U, V, W, B touch: (a, 0) and (0, b) for small a, b and around n, m_I, s_max
     std::map<std::pair<size_t, size_t>, G1Affine> xy_edge;
+    // host copies of what a verifier takes from the reference string (tkmk_prover_verify): the G1Singles section — G, x, y, delta, eta,
+    // lagrange_KL — and the ten G2 records of Sigma2
+    std::array<G1Affine, 6> g1_singles{};
+    std::array<uint8_t, 10 * 192> g2_points{};
     const G1Affine &xy_at(size_t a, size_t b) const {
         auto it = xy_edge.find({a, b});
         if (it == xy_edge.end()) throw Error("xy_powers entry not kept on the host");
@@ -280,6 +284,8 @@ struct ProverSigma {
                            false,
                            {}};
         out.xy_edge = std::move(edge);
+        std::copy(singles, singles + 6, out.g1_singles.begin());
+        std::memcpy(out.g2_points.data(), crs.bytes(CrsPayload::G2Points), out.g2_points.size());
         return out;
     }
 };

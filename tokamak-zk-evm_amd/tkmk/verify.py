@@ -1,0 +1,87 @@
+"""ctypes binding of the verifier's entries of libtkmk_prover.so (include/tkmk_prover.h; host/tkmk_verify.hpp over host/tkmk_pairing.hpp):
+the work-alike of the reference's `verify` (packages/backend/verify-rust/src/lib.rs: Verifier::init + verify_snark) as library calls.
+Host-only — none of the three touches a device; the same code is the binary tokamak-zk-evm_amd/bin/verify.  Nothing here is Python
+beyond the call itself."""
+import ctypes
+import json
+import os
+
+import numpy as np
+
+from tkmk import service
+
+
+def _lib(testing=False):
+    l = service.lib(testing)
+    if not getattr(l, "_tkmk_verify_bound", False):
+        l.tkmk_pairing_product_is_one.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]
+        l.tkmk_verify_files.argtypes = [ctypes.c_char_p] * 5 + [ctypes.c_uint32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p)]
+        l.tkmk_prover_verify.argtypes = [ctypes.c_void_p] + [ctypes.c_char_p] * 3 + [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p)]
+        l._tkmk_verify_bound = True
+    return l
+
+
+def _g1_record(p):
+    if p is None:
+        return bytes(96)
+    b = bytes(np.asarray(p, np.uint8))
+    if len(b) != 96:
+        raise ValueError("a G1 point is a 96-byte affine record (x, y little-endian; all zero = infinity)")
+    return b
+
+
+def _g2_record(q):
+    from tkmk import g2
+    if q is None:
+        return bytes(192)
+    if isinstance(q, tuple):
+        (x0, x1), (y0, y1) = q                 # tkmk.g2 representation; values are NOT reduced here: the library checks the range
+        return b"".join(int(v).to_bytes(48, "little") for v in (x0, x1, y0, y1))
+    b = bytes(np.asarray(q, np.uint8))
+    if len(b) != 192:
+        raise ValueError("a G2 point is a tkmk.g2 point or its 192-byte record")
+    return b
+
+
+def pairing_product_is_one(pairs, testing=False):
+    """pairs: [(P, Q)], P a 96-byte G1 affine record or None, Q a tkmk.g2 point, its 192-byte record or None (None = infinity).
+    -> True iff prod e(P, Q) = 1.  service.ProverError (TKMK_ERR_INVALID_ARGUMENT, the message names index and reason) for a point
+    off its curve, outside the subgroup of order r, or with a coordinate >= p."""
+    l = _lib(testing)
+    g1 = b"".join(_g1_record(p) for p, _ in pairs)
+    g2 = b"".join(_g2_record(q) for _, q in pairs)
+    out = ctypes.c_int(-1)
+    code = l.tkmk_pairing_product_is_one(ctypes.c_char_p(g1) if pairs else None, ctypes.c_char_p(g2) if pairs else None, len(pairs), ctypes.byref(out))
+    if code != 0:
+        raise service.ProverError(code, "tkmk_pairing_product_is_one", testing)
+    return out.value == 1
+
+
+def _take_report(l, doc):
+    rep = json.loads(ctypes.string_at(doc.value).decode())
+    l.tkmk_prover_free_string(doc)
+    return rep
+
+
+def verify_files(subcircuit_library_dir, crs_dir, synthesizer_dir, preprocess_dir, proof_dir, root_generator=0, testing=False):
+    """-> (ok, report): the decision of the reference's `verify` over the same five directories, and the report
+    {"generator", "ok", "reason", "thetas", "kappa0", "chi", "zeta", "kappa1", "a_eval"} (scalars as hex strings).
+    root_generator = 0: TKMK_FR_ROOT_GENERATOR, else the declared default.  service.ProverError for unreadable input."""
+    l = _lib(testing)
+    ok, doc = ctypes.c_int(-1), ctypes.c_void_p()
+    code = l.tkmk_verify_files(os.fsencode(subcircuit_library_dir), os.fsencode(crs_dir), os.fsencode(synthesizer_dir), os.fsencode(preprocess_dir),
+                               os.fsencode(proof_dir), int(root_generator), ctypes.byref(ok), ctypes.byref(doc))
+    if code != 0:
+        raise service.ProverError(code, "tkmk_verify_files", testing)
+    return ok.value == 1, _take_report(l, doc)
+
+
+def prover_verify(prover, synthesizer_dir, preprocess_dir, proof_dir):
+    """the self-check of an open service.Prover: the same decision against the context's own reference string and root-of-unity
+    generator -> (ok, report)"""
+    l = _lib(prover.testing)
+    ok, doc = ctypes.c_int(-1), ctypes.c_void_p()
+    code = l.tkmk_prover_verify(prover._h, os.fsencode(synthesizer_dir), os.fsencode(preprocess_dir), os.fsencode(proof_dir), ctypes.byref(ok), ctypes.byref(doc))
+    if code != 0:
+        raise service.ProverError(code, "tkmk_prover_verify", prover.testing)
+    return ok.value == 1, _take_report(l, doc)
