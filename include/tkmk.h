@@ -396,6 +396,26 @@ tkmk_error tkmk_g1_scale(const tkmk_g1_affine *in_dev, uint64_t n, const tkmk_fr
  * and r jumps only where the copy permutation is not the identity.  in: device, form TKMK_BASES_*; out: device, plain affine; out != in. */
 tkmk_error tkmk_g1_prefix_sums(const tkmk_g1_affine *in_dev, int bases_form, uint32_t rows, uint32_t cols, int transposed,
                                tkmk_g1_affine *out_dev, tkmk_stream stream);
+/* Batched membership test: is every one of n records the all-zero record (infinity: counted, passes) or a canonically stored point of the
+ * prime-order subgroup of y^2 = x^3 + 4?  No reference counterpart (the reference takes its CRS as downloaded, prove/src/sigma_source.rs, and
+ * checks it inside the ceremony only, setup/mpc-setup/src/utils.rs:1447-1476); the audit of host/tkmk_crs_audit.hpp runs it over every G1
+ * table of a reference string.  Per record the FIRST failure is the verdict: a coordinate whose stored integer is >= p (in every form; it is
+ * not reduced and accepted), then the curve equation, then [r]P = infinity — decided on the device by Scott's endomorphism test (ePrint
+ * 2021/1130), which agrees with [r]P = infinity on every point of E(Fq) (csrc/g1check.hip, tests/test_g1_torsion.py).
+ * points_dev: device, form TKMK_BASES_PLAIN / _MONTGOMERY / _CONVERTED (96-byte records; TKMK_BASES_ACC_READY is refused with
+ * TKMK_ERR_INVALID_ARGUMENT); cols, stride = 0, 0: n contiguous records, else element k = row k / cols, column k % cols of a stride-wide
+ * table (stride >= cols), as in tkmk_msm_job_ex.  verdict_dev (optional, device, n bytes) receives 0 or exactly ONE of the bits below per
+ * element.  report_host is written when the call returns (that implies a synchronisation of `stream`); n = 0 is valid and gives the all-zero
+ * report with first_bad = UINT64_MAX.  No library state is read or changed.  Profile section "g1.check". */
+#define TKMK_G1_BAD_NONCANONICAL 1      /* a stored coordinate's limb value is >= p */
+#define TKMK_G1_BAD_OFF_CURVE 2         /* y^2 != x^3 + 4 */
+#define TKMK_G1_BAD_NOT_IN_SUBGROUP 4   /* on the curve, [r]P != infinity */
+typedef struct {
+    uint64_t n_checked, n_infinity, n_noncanonical, n_off_curve, n_not_in_subgroup;
+    uint64_t first_bad;                 /* smallest view index with a non-zero verdict; UINT64_MAX if none */
+} tkmk_g1_check_report;
+tkmk_error tkmk_g1_check(const tkmk_g1_affine *points_dev, int bases_form, uint64_t n, uint32_t cols, uint32_t stride, uint8_t *verdict_dev,
+                         tkmk_g1_check_report *report_host, tkmk_stream stream);
 
 /* ---------------------------------------------------------------------------------------------
  * G2 MSM on BLS12-381 (the twist y^2 = x^3 + 4(1 + u) over Fp2 = Fq[u]/(u^2 + 1)) — ICICLE v3's `bls12_381_g2_msm`
@@ -632,7 +652,7 @@ tkmk_error tkmk_host_free(void *ptr);
  * Measurement hooks (no reference counterpart; the reference's `timing` feature wraps host spans:
  * libs/src/lib.rs:11-141).  When enabled, launchers bracket each kernel with HIP events recorded on the
  * launch stream; names: "msm.digits|hist|scan|scatter|accumulate|reduce_segments|reduce_windows|
- * convert_bases", "ntt.pass<k>".  Recording does not wait for anything (the pipelined MSM entry keeps its overlap);
+ * convert_bases", "ntt.pass<k>", "g1.check".  Recording does not wait for anything (the pipelined MSM entry keeps its overlap);
  * tkmk_profile_get waits for the recorded events and returns the section's summed time and launch count.
  * tkmk_stats_*: what the library was asked to do since the last reset — "msm.points", "msm.calls", "ntt.elements",
  * "ntt.calls" — for the algorithmic-byte figures of the roofline report (128 B per point, 64 B per element).

@@ -53,7 +53,13 @@ typedef struct {          /* seconds */
  * TKMK_ERR_INVALID_ARGUMENT while ANOTHER prover context of the process is open, since that one was built under the generator in effect.
  * None does: TKMK_ERR_INVALID_ARGUMENT, the message names every generator tried; no context is made.  Both do (m_I <= 2 and s_max <= 2):
  * the generator in effect stays.  TKMK_FR_ROOT_GENERATOR=<g> in the environment PINS the convention: that generator alone is tried.
- * tkmk_prover_root_generator tells which generator a context runs under. */
+ * tkmk_prover_root_generator tells which generator a context runs under.
+ * THE RECORDS OF THE CRS ARE TAKEN ON FAITH unless TKMK_PROVER_CHECK_CRS=1 is in the environment: then the audit of tkmk_crs_audit_files
+ * (below) runs on the payload just loaded, before anything is built from it (its own upload of every section: seconds at the production
+ * shape), and a reference string that fails is refused with TKMK_ERR_INVALID_ARGUMENT — the message names the
+ * section, the index and the reason; no context is made.  Unset or 0, open does exactly what it did before the audit existed.
+ * tkmk_prover_open_sharded does NOT read the variable (every rank would audit the whole file): audit the files once, with
+ * tkmk_crs_audit_files or bin/crs-check, before the ranks start. */
 tkmk_error tkmk_prover_open(const char *subcircuit_library_dir, const char *crs_dir, tkmk_prover **out);
 /* ONE proof over the G GPUs of a node (the reference is single-device, so nothing is replaced).  G is a power of
  * two, at most min(n, m_I, s_max).  Rank r of the communicator `comm` (a tkmk_comm of include/tkmk_dist.h, made by the host: one process
@@ -130,6 +136,25 @@ tkmk_error tkmk_verify_files(const char *subcircuit_library_dir, const char *crs
  * work on host copies: no device call, no change to the proving state, no collective — every rank of a sharded context may call it. */
 tkmk_error tkmk_prover_verify(tkmk_prover *p, const char *synthesizer_dir, const char *preprocess_dir, const char *proof_dir, int *ok,
                               char **report_json_out);
+
+
+/* ---- The audit of a reference string (host/tkmk_crs_audit.hpp; needs a device) ----
+ * Reads <lib>/setupParams.json and <crs>/combined_sigma.tkcrs or .rkyv (as tkmk_prover_open does) and decides whether the CRS is well
+ * formed: *ok = 1 iff
+ *   every record of every G1 section (xy_powers, gamma_inv_o_inst, eta_inv_li_o_inter_alpha4_kj, delta_inv_li_o_prv, the three small delta
+ *   tables, the six single points) is canonical, on the curve and in the subgroup of order r (tkmk_g1_check, one upload per section),
+ *   no record of xy_powers is infinity, and the ten G2 points pass the host's checks;
+ *   xy_powers[0] = G, xy_powers[1] = sigma_1.y, xy_powers[rs_y] = sigma_1.x;
+ *   xy_powers is the table [x^a y^b]G: for one grid rho of random scalars, four MSMs over views of the uploaded table (one
+ *   tkmk_msm_multi_ex call) and two pairing products, e(R_y, H) e(-L_y, [y]H) = 1 and e(R_x, H) e(-L_x, [x]H) = 1 — skipped when
+ *   membership failed.  rho expands from a 64-bit seed drawn from getrandom() AT CALL TIME, after the file is fixed; the expansion
+ *   (splitmix64) is not a cryptographic generator.  TKMK_CRS_AUDIT_SEED=<n> fixes the seed in libtkmk_prover_testing.so only.
+ * The gamma / eta / delta tables get membership only: their structure depends on the circuit polynomials.
+ * TKMK_SUCCESS after either verdict; a file that cannot be read or does not match setupParams.json is an error, and so is a machine
+ * without a device (TKMK_ERR_NO_DEVICE).  report_json_out (optional, tkmk_prover_free_string): {"ok", "reason", "sections": [{"name",
+ * "points", "infinity", "noncanonical", "off_curve", "not_in_subgroup", "first_bad"}], "g2", "anchors", "ratio_y", "ratio_x", "seconds":
+ * {"upload", "membership", "g2", "msm", "pairings", "total"}} — null for a step that was not reached, first_bad null when none. */
+tkmk_error tkmk_crs_audit_files(const char *subcircuit_library_dir, const char *crs_dir, int *ok, char **report_json_out);
 
 #ifdef __cplusplus
 }

@@ -10,6 +10,7 @@
 #include <string>
 
 #include "../../include/tkmk_prover.h"
+#include "tkmk_crs_audit.hpp"
 #include "tkmk_crs_load.hpp"
 #include "tkmk_service.hpp"
 #include "tkmk_verify.hpp"
@@ -56,7 +57,16 @@ TKP_API tkmk_error tkmk_prover_open(const char *subcircuit_library_dir, const ch
         std::string crs = crs_dir;
         DefaultStreamTurn turn(false);
         std::unique_ptr<tkmk_prover> p(new tkmk_prover());
-        p->ctx = ProverContext::open(subcircuit_library_dir, crs, [&](const SetupParams &sp, std::string &source, const CrsGridHook &hook) { return load_prover_sigma(crs, sp, source, resident_table_c(sp), Shard{}, nullptr, hook); });
+        // TKMK_PROVER_CHECK_CRS=1: the audit of tkmk_crs_audit.hpp over the payload just loaded, before anything of it is uploaded for the
+        // prover; a CRS that fails is refused and no context is made.  Unset or 0: nothing is added to what open does.
+        CrsPayloadHook audit;
+        if (crs_audit::requested_at_open())
+            audit = [&](const CrsPayload &payload) {
+                crs_audit::Report rep;
+                const SetupParams sp = crs_audit::read_setup_params(subcircuit_library_dir);
+                if (!crs_audit::audit_payload(payload, sp, rep)) throw Error("tkmk_prover_open: the reference string failed its audit (TKMK_PROVER_CHECK_CRS): " + rep.reason);
+            };
+        p->ctx = ProverContext::open(subcircuit_library_dir, crs, [&](const SetupParams &sp, std::string &source, const CrsGridHook &hook) { return load_prover_sigma(crs, sp, source, resident_table_c(sp), Shard{}, nullptr, hook, audit); });
         *out = p.release();
     });
 }
@@ -207,6 +217,22 @@ TKP_API tkmk_error tkmk_verify_files(const char *subcircuit_library_dir, const c
         verify::Report rep;
         const bool verdict = verify::verify_files(subcircuit_library_dir, crs_dir, synthesizer_dir, preprocess_dir, proof_dir, root_generator, rep);
         hand_over(verdict, rep, ok, report_json_out);
+    });
+}
+
+// the CRS audit (host/tkmk_crs_audit.hpp): device work on the default stream, so it takes the unsharded contexts' turn
+TKP_API tkmk_error tkmk_crs_audit_files(const char *subcircuit_library_dir, const char *crs_dir, int *ok, char **report_json_out) {
+    if (!subcircuit_library_dir || !crs_dir || !ok) return TKMK_ERR_INVALID_POINTER;
+    *ok = 0;
+    if (report_json_out) *report_json_out = nullptr;
+    return guarded([&] {
+        int ndev = 0;
+        if (tkmk_device_count(&ndev) != TKMK_SUCCESS || ndev < 1) throw Error(TKMK_ERR_NO_DEVICE, "tkmk_crs_audit_files: no HIP device (the MI355X backend has no CPU fallback)");
+        DefaultStreamTurn turn(false);
+        crs_audit::Report rep;
+        const bool verdict = crs_audit::audit_files(subcircuit_library_dir, crs_dir, rep);
+        if (report_json_out) *report_json_out = dup_string(rep.to_json());
+        *ok = verdict ? 1 : 0;
     });
 }
 

@@ -47,10 +47,15 @@ inline CrsPayload load_combined_sigma(const std::string &crs_dir, const SetupPar
 }
 // table_c: window width of the precomputed commit table (0 = none): worth its one-time cost (seconds) and memory (13 x xy_powers at
 // 20 bits) only for a prover that stays resident
+// on_payload (optional) sees the loaded sections before anything is uploaded; it refuses the CRS by throwing (the audit of
+// tkmk_crs_audit.hpp under TKMK_PROVER_CHECK_CRS=1)
+using CrsPayloadHook = std::function<void(const CrsPayload &)>;
 inline std::unique_ptr<ProverSigma> load_prover_sigma(const std::string &crs_dir, const SetupParams &sp, std::string &source, uint32_t table_c = 0,
-                                                      Shard shard = Shard{}, std::unique_ptr<Sigma1> *whole_grid = nullptr, const CrsGridHook &on_grid = CrsGridHook()) {
+                                                      Shard shard = Shard{}, std::unique_ptr<Sigma1> *whole_grid = nullptr, const CrsGridHook &on_grid = CrsGridHook(),
+                                                      const CrsPayloadHook &on_payload = CrsPayloadHook()) {
     CrsPayload crs = load_combined_sigma(crs_dir, sp);
     source = crs.container;
+    if (on_payload) on_payload(crs);
     return std::unique_ptr<ProverSigma>(new ProverSigma(ProverSigma::from_payload(crs, sp, table_c, shard, whole_grid, on_grid)));
 }
 // the resident prover's default: 20-bit windows once xy_powers is large enough for the wide sort to pay (>= 2^20 points);

@@ -100,7 +100,7 @@ SYMBOLS = [
     "tkmk_msm_multi_ex", "bls12_381_msm_convert_bases", "tkmk_r1cs_library_create", "tkmk_r1cs_library_destroy", "tkmk_r1cs_library_eval",
     "tkmk_witness_route", "tkmk_fr_scatter_table", "tkmk_msm_set_pipeline_streams", "tkmk_msm_get_pipeline_streams", "tkmk_host_malloc", "tkmk_host_free", "tkmk_stats_reset", "tkmk_stats_get",
     "bls12_381_ntt_domain_size", "bn254_ntt_domain_size", "tkmk_poly_lincomb", "tkmk_bintt_padded", "tkmk_diag_device_switch", "tkmk_diag_gather_probe",
-    "bls12_381_get_root_of_unity_with_generator", "tkmk_ntt_root_generator", "tkmk_ntt_set_root_generator", "tkmk_poly_geometric_grid", "tkmk_crs_identify_root",
+    "bls12_381_get_root_of_unity_with_generator", "tkmk_ntt_root_generator", "tkmk_ntt_set_root_generator", "tkmk_poly_geometric_grid", "tkmk_crs_identify_root", "tkmk_g1_check",
     "bls12_381_generate_random_affine_points", "bls12_381_generate_scalars", "bls12_381_polynomial_add", "bls12_381_polynomial_clone", "bls12_381_polynomial_coeffs_device_ptr", "bls12_381_polynomial_copy_coeffs", "bls12_381_polynomial_create_from_coefficients", "bls12_381_polynomial_create_from_rou_evaluations", "bls12_381_polynomial_degree", "bls12_381_polynomial_delete", "bls12_381_polynomial_divide", "bls12_381_polynomial_evaluate", "bls12_381_polynomial_get_coeff", "bls12_381_polynomial_multiply", "bls12_381_polynomial_multiply_by_scalar", "bls12_381_polynomial_nof_coeffs", "bls12_381_polynomial_slice", "bls12_381_polynomial_subtract", "bls12_381_vector_accumulate",
 ]
 
@@ -503,6 +503,31 @@ def g1_scale(points, n, scalar, out=None):
     sc = np.ascontiguousarray(np.frombuffer(bytes(scalar), np.uint8))
     _check(lib().tkmk_g1_scale(_p(points), ctypes.c_uint64(n), _p(sc), _p(out), None), "tkmk_g1_scale")
     return out
+
+
+class G1CheckReport(ctypes.Structure):
+    _fields_ = [("n_checked", ctypes.c_uint64), ("n_infinity", ctypes.c_uint64), ("n_noncanonical", ctypes.c_uint64),
+                ("n_off_curve", ctypes.c_uint64), ("n_not_in_subgroup", ctypes.c_uint64), ("first_bad", ctypes.c_uint64)]
+
+
+G1_BAD_NONCANONICAL, G1_BAD_OFF_CURVE, G1_BAD_NOT_IN_SUBGROUP = 1, 2, 4
+
+
+def g1_check(points, bases_form=0, cols=0, stride=0, want_verdicts=True, n=None, stream=None):
+    """tkmk_g1_check: membership of every record of `points` (host array or DeviceBuffer of 96-byte affine records in bases_form) in the
+    prime-order subgroup.  cols, stride = 0, 0: all records (or the first n); else n (default: every whole row) elements of the view "row
+    k // cols, column k % cols of a stride-wide table".  Returns (report dict, verdict bytes or None): per record 0, G1_BAD_NONCANONICAL,
+    G1_BAD_OFF_CURVE or G1_BAD_NOT_IN_SUBGROUP; infinity records pass and are counted"""
+    records = _len(points) * 32 // 96
+    if n is None:
+        n = records // stride * cols if cols else records
+    dev = points if _on_dev(points) or not records else DeviceBuffer.from_host(points)
+    verdicts = DeviceBuffer(max(n, 1)) if want_verdicts else None
+    rep = G1CheckReport()
+    _check(lib().tkmk_g1_check(_p(dev) if records else None, int(bases_form), ctypes.c_uint64(n), ctypes.c_uint32(cols), ctypes.c_uint32(stride),
+                               _p(verdicts), ctypes.byref(rep), stream), "tkmk_g1_check")
+    report = {k: int(getattr(rep, k)) for k, _ in G1CheckReport._fields_}
+    return report, (verdicts.to_host(n) if n else np.empty(0, np.uint8)) if want_verdicts else None
 
 
 def msm_g2(scalars, bases, msm_size=None, batch=1, shared_points=True, c=0, bitsize=0, stream=None, scalars_montgomery=False,

@@ -17,6 +17,7 @@ def _lib(testing=False):
         l.tkmk_pairing_product_is_one.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]
         l.tkmk_verify_files.argtypes = [ctypes.c_char_p] * 5 + [ctypes.c_uint32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p)]
         l.tkmk_prover_verify.argtypes = [ctypes.c_void_p] + [ctypes.c_char_p] * 3 + [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p)]
+        l.tkmk_crs_audit_files.argtypes = [ctypes.c_char_p] * 2 + [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p)]
         l._tkmk_verify_bound = True
     return l
 
@@ -73,6 +74,20 @@ def verify_files(subcircuit_library_dir, crs_dir, synthesizer_dir, preprocess_di
                                os.fsencode(proof_dir), int(root_generator), ctypes.byref(ok), ctypes.byref(doc))
     if code != 0:
         raise service.ProverError(code, "tkmk_verify_files", testing)
+    return ok.value == 1, _take_report(l, doc)
+
+
+def crs_audit(subcircuit_library_dir, crs_dir, testing=False):
+    """-> (ok, report): tkmk_crs_audit_files — is the reference string <crs_dir>/combined_sigma.{tkcrs, rkyv} well formed for the circuit of
+    <subcircuit_library_dir>: membership of every G1 record on the device (tkmk_g1_check) and of the ten G2 points on the host, the anchors,
+    and the power structure of xy_powers by four MSMs and two pairing products.  report = {"ok", "reason", "sections": [{"name", "points",
+    "infinity", "noncanonical", "off_curve", "not_in_subgroup", "first_bad"}], "g2", "anchors", "ratio_y", "ratio_x", "seconds"}.  Needs a
+    device; service.ProverError for unreadable input.  testing=True: libtkmk_prover_testing.so, which honours TKMK_CRS_AUDIT_SEED."""
+    l = _lib(testing)
+    ok, doc = ctypes.c_int(-1), ctypes.c_void_p()
+    code = l.tkmk_crs_audit_files(os.fsencode(subcircuit_library_dir), os.fsencode(crs_dir), ctypes.byref(ok), ctypes.byref(doc))
+    if code != 0:
+        raise service.ProverError(code, "tkmk_crs_audit_files", testing)
     return ok.value == 1, _take_report(l, doc)
 
 
