@@ -627,6 +627,22 @@ tkmk_error tkmk_r1cs_library_destroy(tkmk_r1cs_library *lib);
 tkmk_error tkmk_r1cs_library_eval(const tkmk_r1cs_library *lib, const tkmk_fr *vars_dev, const uint32_t *placement_id_dev,
                                   const uint64_t *placement_var_offset_dev, uint32_t n_placements, uint32_t n, uint32_t s_max,
                                   tkmk_fr *u_dev, tkmk_fr *v_dev, tkmk_fr *w_dev, tkmk_stream stream);
+/* The transpose-free twin of _eval for WEIGHTS PER WIRE instead of values per placement (csrc/crsaudit.hip; the circuit part of the CRS
+ * audit, host/tkmk_crs_audit.hpp): with weight_dev[kind] a device vector of n_wires[kind] plain Fr and col_dev[kind] a device array of
+ * n_wires[kind] bytes naming the output column of each wire (col_dev == NULL or col_dev[kind] == NULL: column 0),
+ *   u[c * out_stride + g] = sum over kinds, over the entries k of row c of A_kind with col(wire_k) = g, of coeff_k * weight[kind][wire_k]
+ * and v, w likewise from B and C.  _eval gives every placement its own slot: it can neither sum kinds nor route by wire.  weight_dev and
+ * col_dev themselves are HOST arrays of n_sub device pointers.  Every element of [0, n) x [0, n_cols) is written, zeros included; nothing
+ * outside it is touched.  Rows past a kind's n_rows contribute nothing.  One lane per (row, matrix) walks the kinds in order: the result
+ * does not depend on scheduling.  TKMK_ERR_INVALID_ARGUMENT for n_cols == 0, n_cols > out_stride, n_cols > 255, a kind with more than n
+ * rows, and a col value >= n_cols (the arrays are read back and checked on the host before the launch).  Returns after the kernel. */
+tkmk_error tkmk_r1cs_library_mix(const tkmk_r1cs_library *lib, const tkmk_fr *const *weight_dev, const uint8_t *const *col_dev, uint32_t n,
+                                 uint32_t n_cols, uint32_t out_stride, tkmk_fr *u_dev, tkmk_fr *v_dev, tkmk_fr *w_dev, tkmk_stream stream);
+/* out_dev[j * out_stride + i] = col_dev[j] * row_dev[i], j < rows, i < cols (plain Fr, device pointers; out_stride >= cols, the padding
+ * is not touched): the rank-one grids of the CRS audit.  The setup's outer product (host/tkmk_setup.hpp outer_scaled) stages two host
+ * index arrays of rows * cols entries for the same result. */
+tkmk_error tkmk_fr_outer(const tkmk_fr *col_dev, uint32_t rows, const tkmk_fr *row_dev, uint32_t cols, uint32_t out_stride, tkmk_fr *out_dev,
+                         tkmk_stream stream);
 /* Routes witness values by a static (local wire, row) list of one subcircuit kind, for the n_placements placements of that kind
  * (variables at var_offset_dev[i], global placement index slot_dev[i]):
  *   matrix_dev      (optional): matrix_dev[row * matrix_stride + slot] = value — gen_bXY's interface-wire matrix

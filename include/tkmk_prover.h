@@ -58,6 +58,8 @@ typedef struct {          /* seconds */
  * (below) runs on the payload just loaded, before anything is built from it (its own upload of every section: seconds at the production
  * shape), and a reference string that fails is refused with TKMK_ERR_INVALID_ARGUMENT — the message names the
  * section, the index and the reason; no context is made.  Unset or 0, open does exactly what it did before the audit existed.
+ * TKMK_PROVER_CHECK_CRS=2 runs the audit of tkmk_crs_audit_circuit_files instead: the same, then the gamma / eta / delta tables against the
+ * circuit of subcircuit_library_dir (which must hold subcircuitInfo.json and r1cs/); a table that fails is named in the message.
  * tkmk_prover_open_sharded does NOT read the variable (every rank would audit the whole file): audit the files once, with
  * tkmk_crs_audit_files or bin/crs-check, before the ranks start. */
 tkmk_error tkmk_prover_open(const char *subcircuit_library_dir, const char *crs_dir, tkmk_prover **out);
@@ -149,12 +151,32 @@ tkmk_error tkmk_prover_verify(tkmk_prover *p, const char *synthesizer_dir, const
  *   tkmk_msm_multi_ex call) and two pairing products, e(R_y, H) e(-L_y, [y]H) = 1 and e(R_x, H) e(-L_x, [x]H) = 1 — skipped when
  *   membership failed.  rho expands from a 64-bit seed drawn from getrandom() AT CALL TIME, after the file is fixed; the expansion
  *   (splitmix64) is not a cryptographic generator.  TKMK_CRS_AUDIT_SEED=<n> fixes the seed in libtkmk_prover_testing.so only.
- * The gamma / eta / delta tables get membership only: their structure depends on the circuit polynomials.
+ * This entry gives the gamma / eta / delta tables membership only: their structure depends on the circuit polynomials, which
+ * tkmk_crs_audit_circuit_files (below) reads.
  * TKMK_SUCCESS after either verdict; a file that cannot be read or does not match setupParams.json is an error, and so is a machine
  * without a device (TKMK_ERR_NO_DEVICE).  report_json_out (optional, tkmk_prover_free_string): {"ok", "reason", "sections": [{"name",
  * "points", "infinity", "noncanonical", "off_curve", "not_in_subgroup", "first_bad"}], "g2", "anchors", "ratio_y", "ratio_x", "seconds":
- * {"upload", "membership", "g2", "msm", "pairings", "total"}} — null for a step that was not reached, first_bad null when none. */
+ * {"upload", "membership", "g2", "msm", "pairings", "total"}, "circuit", "tables", "table_seconds"} — null for a step that was not
+ * reached, first_bad null when none; the last three keys are null from this entry. */
 tkmk_error tkmk_crs_audit_files(const char *subcircuit_library_dir, const char *crs_dir, int *ok, char **report_json_out);
+/* The same contract, plus the table checks against the circuit: needs <lib>/subcircuitInfo.json and <lib>/r1cs/subcircuit{id}.r1cs as well
+ * (a missing or malformed file is an error return, not a verdict).  After everything above has passed — the table checks rest on
+ * xy_powers being right, which stays on the device through them — every record of the seven G1 tables is tied to the circuit:
+ *   gamma, eta, delta   a random combination of the table (weights a_j per flattened wire, b_i per placement column: the rank-one grid
+ *                       a_j b_i) against MSMs over xy_powers of the circuit's own polynomials — tkmk_r1cs_library_mix and tkmk_fr_outer build
+ *                       the evaluation grids, tkmk_bintt turns them into coefficients — through one pairing product per table against
+ *                       [gamma]H, [eta]H, [delta]H and [alpha^k]H;
+ *   delta_small         the 9 + 2 + 12 records of the three small delta tables against differences of xy_powers records (an infinity
+ *                       record among them is a failure);
+ *   alpha_chain         sigma_2.alpha .. alpha4 are powers of one alpha;
+ *   singles             sigma_1.delta and sigma_1.eta are [delta]G and [eta]G for the delta and eta of sigma_2.
+ * The root of unity the Lagrange bases are taken over is identified from the CRS first, as tkmk_prover_open does (a CRS made under
+ * generator 7 audits as one made under 5; adopting it is process-wide).  Together this fixes all seven G1 tables and the single points,
+ * and sigma_2 except that gamma, delta, eta are tied to the tables only, not to each other.  NOT covered: sigma_preprocess.rkyv, the
+ * sharded open, BN254.  Which record of a failed table is wrong is not located.  The seed caveat above holds unchanged.
+ * Report: "circuit" true / false (null when an earlier step failed), "tables": [{"name", "points", "ok"}] for gamma, eta, delta,
+ * delta_small, alpha_chain, singles (an empty table is vacuously ok with 0 points), "table_seconds": {"library", "grids", "msm", "pairings"}. */
+tkmk_error tkmk_crs_audit_circuit_files(const char *subcircuit_library_dir, const char *crs_dir, int *ok, char **report_json_out);
 
 #ifdef __cplusplus
 }

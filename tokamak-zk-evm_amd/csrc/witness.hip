@@ -15,15 +15,7 @@
 #include <vector>
 
 #include "common.h"
-
-struct tkmk_r1cs_library {
-    uint32_t n_sub = 0, max_rows = 0;
-    uint32_t *d_rowptr = nullptr;    // concatenated row_ptr arrays, (n_rows + 1) each, order [sub][matrix]
-    uint32_t *d_wire = nullptr;      // concatenated wire arrays
-    fr_t *d_coeff = nullptr;         // concatenated coefficients, Montgomery form
-    uint32_t *d_desc = nullptr;      // per (sub, matrix): {rowptr base, entry base}; per sub: n_rows, n_wires  -> 8 u32 per sub
-    std::vector<uint32_t> n_rows, n_wires;
-};
+#include "r1cs_library.h"
 
 // desc layout per subcircuit: [0..2] rowptr base of A,B,C; [3..5] entry base of A,B,C; [6] n_rows; [7] n_wires
 __global__ __launch_bounds__(256) void k_r1cs_library_eval(const uint32_t *__restrict__ rowptr, const uint32_t *__restrict__ wire,

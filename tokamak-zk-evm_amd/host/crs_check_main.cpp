@@ -1,7 +1,8 @@
 // crs_check_main.cpp — `crs-check`: is the reference string of a directory well formed for a circuit?  (host/tkmk_crs_audit.hpp)
-//   crs-check --crs DIR [--subcircuit-library DIR]
+//   crs-check --crs DIR [--subcircuit-library DIR] [--circuit]
 // Reads <lib>/setupParams.json and <crs>/combined_sigma.tkcrs or combined_sigma.rkyv, as `prove` does; without --subcircuit-library the
-// library is resolved the way host/tkmk_args.hpp describes.  No reference counterpart: the reference downloads its CRS at install
+// library is resolved the way host/tkmk_args.hpp describes.  --circuit adds the table checks of the gamma / eta / delta tables against the
+// circuit (reads <lib>/subcircuitInfo.json and <lib>/r1cs/ as well; one more stderr line per table).  No reference counterpart: the reference downloads its CRS at install
 // (setup/mpc-setup/src/drive_upload.rs) and checks it inside the ceremony only.
 // stdout: the directory lines, then `true` or `false` as the LAST line, as bin/verify prints its verdict.  stderr: one line per section
 // (points, infinity, not reduced, off the curve, outside the subgroup), the steps' verdicts and times, and the reason for `false`.
@@ -15,12 +16,13 @@
 using namespace tkmk;
 
 static const char *USAGE =
-    "Usage: crs-check --crs <PATH> [--subcircuit-library <PATH>]\n"
+    "Usage: crs-check --crs <PATH> [--subcircuit-library <PATH>] [--circuit]\n"
     "  --crs                 CRS directory containing combined_sigma.rkyv (or combined_sigma.tkcrs)\n"
-    "  --subcircuit-library  Subcircuit library directory produced by the QAP compiler (default: see host/tkmk_args.hpp)\n";
+    "  --subcircuit-library  Subcircuit library directory produced by the QAP compiler (default: see host/tkmk_args.hpp)\n"
+    "  --circuit             Also check the gamma / eta / delta tables against the circuit of the library (reads its r1cs/ files)\n";
 
 int main(int argc, char **argv) {
-    args::Spec spec{{"--crs", "--subcircuit-library"}, {}};
+    args::Spec spec{{"--crs", "--subcircuit-library"}, {"--circuit"}};
     args::Parsed a = args::parse(argc, argv, spec);
     if (a.help) {
         fputs(USAGE, stdout);
@@ -44,7 +46,7 @@ int main(int argc, char **argv) {
         fflush(stdout);
         crs_audit::Report rep;
         std::string container;
-        const bool ok = crs_audit::audit_files(lib_dir, a.get("--crs"), rep, &container);
+        const bool ok = crs_audit::audit_files(lib_dir, a.get("--crs"), rep, &container, a.flag("--circuit"));
         fprintf(stderr, "crs-check: %s\n", container.c_str());
         auto word = [](int v) { return v < 0 ? "not reached" : v ? "ok" : "FAILED"; };
         for (const crs_audit::SectionReport &s : rep.sections)
@@ -55,6 +57,13 @@ int main(int argc, char **argv) {
                 word(rep.ratio_x));
         fprintf(stderr, "crs-check: upload %.3f s, membership %.3f s, g2 %.3f s, four MSMs %.3f s, pairings %.3f s, total %.3f s\n", rep.upload_s, rep.membership_s,
                 rep.g2_s, rep.msm_s, rep.pairing_s, rep.total_s);
+        if (rep.circuit >= 0) {
+            for (const crs_audit::TableReport &t : rep.tables)
+                fprintf(stderr, "crs-check: table %-19s %10llu points, %s\n", t.name.c_str(), (unsigned long long)t.points,
+                        !t.ok ? "FAILED" : t.points ? "ok" : "ok (empty: vacuously true)");
+            fprintf(stderr, "crs-check: tables: library %.3f s, grids %.3f s, MSMs %.3f s, pairings %.3f s\n", rep.t_library_s, rep.t_grids_s, rep.t_msm_s,
+                    rep.t_pairing_s);
+        }
         if (!ok) fprintf(stderr, "crs-check: %s\n", rep.reason.c_str());
         printf("%s\n", ok ? "true" : "false");
         return 0;

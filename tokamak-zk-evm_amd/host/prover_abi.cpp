@@ -58,13 +58,14 @@ TKP_API tkmk_error tkmk_prover_open(const char *subcircuit_library_dir, const ch
         DefaultStreamTurn turn(false);
         std::unique_ptr<tkmk_prover> p(new tkmk_prover());
         // TKMK_PROVER_CHECK_CRS=1: the audit of tkmk_crs_audit.hpp over the payload just loaded, before anything of it is uploaded for the
-        // prover; a CRS that fails is refused and no context is made.  Unset or 0: nothing is added to what open does.
+        // prover; a CRS that fails is refused and no context is made.  =2: with the table checks against the circuit of the library.
+        // Unset or 0: nothing is added to what open does.
         CrsPayloadHook audit;
         if (crs_audit::requested_at_open())
             audit = [&](const CrsPayload &payload) {
                 crs_audit::Report rep;
                 const SetupParams sp = crs_audit::read_setup_params(subcircuit_library_dir);
-                if (!crs_audit::audit_payload(payload, sp, rep)) throw Error("tkmk_prover_open: the reference string failed its audit (TKMK_PROVER_CHECK_CRS): " + rep.reason);
+                if (!crs_audit::audit_payload(payload, sp, rep, crs_audit::circuit_requested_at_open(), subcircuit_library_dir)) throw Error("tkmk_prover_open: the reference string failed its audit (TKMK_PROVER_CHECK_CRS): " + rep.reason);
             };
         p->ctx = ProverContext::open(subcircuit_library_dir, crs, [&](const SetupParams &sp, std::string &source, const CrsGridHook &hook) { return load_prover_sigma(crs, sp, source, resident_table_c(sp), Shard{}, nullptr, hook, audit); });
         *out = p.release();
@@ -221,19 +222,26 @@ TKP_API tkmk_error tkmk_verify_files(const char *subcircuit_library_dir, const c
 }
 
 // the CRS audit (host/tkmk_crs_audit.hpp): device work on the default stream, so it takes the unsharded contexts' turn
-TKP_API tkmk_error tkmk_crs_audit_files(const char *subcircuit_library_dir, const char *crs_dir, int *ok, char **report_json_out) {
+static tkmk_error crs_audit_entry(const char *entry, const char *subcircuit_library_dir, const char *crs_dir, bool circuit, int *ok, char **report_json_out) {
     if (!subcircuit_library_dir || !crs_dir || !ok) return TKMK_ERR_INVALID_POINTER;
     *ok = 0;
     if (report_json_out) *report_json_out = nullptr;
     return guarded([&] {
         int ndev = 0;
-        if (tkmk_device_count(&ndev) != TKMK_SUCCESS || ndev < 1) throw Error(TKMK_ERR_NO_DEVICE, "tkmk_crs_audit_files: no HIP device (the MI355X backend has no CPU fallback)");
+        if (tkmk_device_count(&ndev) != TKMK_SUCCESS || ndev < 1) throw Error(TKMK_ERR_NO_DEVICE, std::string(entry) + ": no HIP device (the MI355X backend has no CPU fallback)");
         DefaultStreamTurn turn(false);
         crs_audit::Report rep;
-        const bool verdict = crs_audit::audit_files(subcircuit_library_dir, crs_dir, rep);
+        const bool verdict = crs_audit::audit_files(subcircuit_library_dir, crs_dir, rep, nullptr, circuit);
         if (report_json_out) *report_json_out = dup_string(rep.to_json());
         *ok = verdict ? 1 : 0;
     });
+}
+TKP_API tkmk_error tkmk_crs_audit_files(const char *subcircuit_library_dir, const char *crs_dir, int *ok, char **report_json_out) {
+    return crs_audit_entry("tkmk_crs_audit_files", subcircuit_library_dir, crs_dir, false, ok, report_json_out);
+}
+// ... plus the gamma / eta / delta tables against the circuit of the library (audit_tables)
+TKP_API tkmk_error tkmk_crs_audit_circuit_files(const char *subcircuit_library_dir, const char *crs_dir, int *ok, char **report_json_out) {
+    return crs_audit_entry("tkmk_crs_audit_circuit_files", subcircuit_library_dir, crs_dir, true, ok, report_json_out);
 }
 
 TKP_API tkmk_error tkmk_prover_verify(tkmk_prover *p, const char *synthesizer_dir, const char *preprocess_dir, const char *proof_dir, int *ok,

@@ -87,22 +87,9 @@ int main(int argc, char **argv) {
         SetupParams sp{jp.at("l").as_size(),   jp.at("l_user_out").as_size(), jp.at("l_user").as_size(), jp.at("l_free").as_size(),
                        jp.at("l_D").as_size(), jp.at("m_D").as_size(),        jp.at("n").as_size(),      jp.at("s_D").as_size(),
                        jp.at("s_max").as_size()};
-        std::vector<SubcircuitInfo> infos;
-        std::vector<size_t> n_consts;
-        {
-            const json::Value jinfo = json::read_file(lib_dir + "/subcircuitInfo.json");
-            for (const json::Value &e : jinfo.items()) {
-                SubcircuitInfo si;
-                si.id = e.at("id").as_size();
-                si.name = e.at("name").as_string();
-                si.Nwires = e.at("Nwires").as_size();
-                si.Out_idx = {e.at("Out_idx").items().at(0).as_size(), e.at("Out_idx").items().at(1).as_size()};
-                si.In_idx = {e.at("In_idx").items().at(0).as_size(), e.at("In_idx").items().at(1).as_size()};
-                for (const json::Value &g : e.at("flattenMap").items()) si.flattenMap.push_back(g.as_size());
-                infos.push_back(std::move(si));
-                n_consts.push_back(e.at("Nconsts").as_size());
-            }
-        }
+        const SubcircuitLibrary library = SubcircuitLibrary::read_infos(lib_dir);
+        const std::vector<SubcircuitInfo> &infos = library.infos;
+        const std::vector<size_t> &n_consts = library.n_consts;
         Tau tau;
         G1Affine g1;
         g2h::Affine h2;

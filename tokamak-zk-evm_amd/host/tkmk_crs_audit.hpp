@@ -1,5 +1,5 @@
 // tkmk_crs_audit.hpp — is this reference string well formed?  The audit behind tkmk_crs_audit_files (include/tkmk_prover.h), bin/crs-check
-// and the TKMK_PROVER_CHECK_CRS=1 opt-in of tkmk_prover_open, over a CrsPayload as load_combined_sigma returns it (either container).
+// and the TKMK_PROVER_CHECK_CRS=1 / =2 opt-in of tkmk_prover_open, over a CrsPayload as load_combined_sigma returns it (either container).
 // The reference downloads its CRS (setup/mpc-setup/src/drive_upload.rs, prove/src/sigma_source.rs) and verifies the power structure only
 // inside the ceremony (setup/mpc-setup/src/utils.rs:1447-1476, same_ratio / consistent); the prover uploads millions of records it never
 // looks at.  A CRS with one bad record gives no error: it gives proofs that fail on chain.
@@ -22,8 +22,26 @@
 // without knowledge of the seed (64 bits of it), not against an adversary who can predict or observe the seed before fixing the file.
 // TKMK_CRS_AUDIT_SEED=<n> replaces the seed in the -DTKMK_TESTING_MODE build only (as the fixed-blinding hook: the production library
 // ignores it).
-// OUT OF SCOPE: the structure of the gamma / eta / delta tables depends on the circuit polynomials; they get membership only.  A sharded
-// prover does not audit (tkmk_prover_open_sharded does not read the variable): audit the files once before the ranks start.
+//   CIRCUIT     (opt-in: `circuit` / crs-check --circuit / tkmk_crs_audit_circuit_files / TKMK_PROVER_CHECK_CRS=2; needs <lib>/subcircuitInfo.json
+//               and <lib>/r1cs/)  the gamma / eta / delta tables are the only part of a reference string that ties it to THIS circuit, and every
+//               binding commitment is computed from them.  Every record is s^-1 f(x, y, alpha) with s one of gamma, eta, delta and f a
+//               polynomial whose coefficients come from the .r1cs files, so a random combination of a table is compared with MSMs over the
+//               already verified xy_powers through one pairing product per table (audit_tables below, Sigma::gen of tkmk_setup.hpp being
+//               the definition mirrored):
+//                 eta          e(sum a_{l+j} b_i T[j s_max + i], [eta]H) = e(PU, [alpha]H) e(PV, [alpha^2]H) e(PW, [alpha^3]H) e(PK, [alpha^4]H)
+//                 delta        the same over the private wires, without the K term, against [delta]H (an empty table is vacuously true)
+//                 gamma        e(sum a_j T[j], [gamma]H) = e(PU, [alpha]H) e(PV, [alpha^2]H) e(PW, [alpha^3]H) e(PM, H)
+//                 delta_small  the 9 + 2 + 12 records of the three small delta tables against differences of xy_powers records
+//                 alpha_chain  e(sum d_k yi[3(k-1)], [alpha]H) = e(sum d_k yi[3k], H): with delta_small, [alpha^2]H .. [alpha^4]H are powers of alpha
+//                 singles      e(sigma_1.delta, H) = e(G, [delta]H), e(sigma_1.eta, H) = e(G, [eta]H)
+//               PU / PV / PW = [sum_c sum_i E[c][i] L_c(x) L_i(y)]G: the evaluation grid E (tkmk_r1cs_library_mix over per-wire weights, times b
+//               through tkmk_fr_outer) -> tkmk_bintt inverse -> one MSM over the view of xy_powers.  The rank-one weights a_j b_i are
+//               enough: a non-zero error table survives a random bilinear form except with probability ~ 2 / r.  The root of unity L, K, M
+//               depend on is identified from the CRS first (identify_crs_root), as `prove` and `preprocess` do.  A failure says which
+//               table; WHICH record of it is wrong is not located.
+//               What this fixes: all seven G1 tables and the single points, and sigma_2 except that gamma, delta, eta are tied to the tables
+//               only, not to each other.  Not covered: sigma_preprocess.rkyv, the sharded open, BN254.
+// A sharded prover does not audit (tkmk_prover_open_sharded does not read the variable): audit the files once before the ranks start.
 #pragma once
 #include <sys/random.h>
 
@@ -38,12 +56,20 @@ struct SectionReport {
     std::string name;
     tkmk_g1_check_report r{};
 };
+struct TableReport {
+    std::string name;   // gamma, eta, delta, delta_small, alpha_chain, singles
+    uint64_t points = 0;
+    bool ok = false;
+};
 struct Report {
     bool ok = false;
     std::string reason;                    // for ok == false: section, index, what is wrong
     std::vector<SectionReport> sections;   // in the order they were checked
     int g2 = -1, anchors = -1, ratio_y = -1, ratio_x = -1;   // -1: not reached (JSON null)
     double upload_s = 0, membership_s = 0, g2_s = 0, msm_s = 0, pairing_s = 0, total_s = 0;
+    int circuit = -1;                      // the table checks against the circuit: -1 not asked for or not reached, else their verdict
+    std::vector<TableReport> tables;       // in the order they were checked (empty unless the table checks ran)
+    double t_library_s = 0, t_grids_s = 0, t_msm_s = 0, t_pairing_s = 0;
     std::string to_json() const {
         auto esc = [](const std::string &s) {
             std::string o;
@@ -70,6 +96,14 @@ struct Report {
         d += "], \"g2\": " + tri(g2) + ", \"anchors\": " + tri(anchors) + ", \"ratio_y\": " + tri(ratio_y) + ", \"ratio_x\": " + tri(ratio_x);
         d += ", \"seconds\": {\"upload\": " + num(upload_s) + ", \"membership\": " + num(membership_s) + ", \"g2\": " + num(g2_s) + ", \"msm\": " + num(msm_s) +
              ", \"pairings\": " + num(pairing_s) + ", \"total\": " + num(total_s) + "}";
+        d += ", \"circuit\": " + tri(circuit);
+        if (circuit < 0) return d + ", \"tables\": null, \"table_seconds\": null}";
+        d += ", \"tables\": [";
+        for (size_t k = 0; k < tables.size(); k++)
+            d += std::string(k ? ", " : "") + "{\"name\": \"" + tables[k].name + "\", \"points\": " + std::to_string(tables[k].points) + ", \"ok\": " +
+                 (tables[k].ok ? "true" : "false") + "}";
+        d += "], \"table_seconds\": {\"library\": " + num(t_library_s) + ", \"grids\": " + num(t_grids_s) + ", \"msm\": " + num(t_msm_s) + ", \"pairings\": " +
+             num(t_pairing_s) + "}";
         return d + "}";
     }
 };
@@ -102,9 +136,282 @@ inline bool pairing_product_is_one(const G1Affine *p, const uint8_t *const *q192
     return pairing::product_is_one(pairs);
 }
 
+// ---- the table checks against the circuit (CIRCUIT above) ----
+struct DeviceLibrary {   // tkmk_r1cs_library with its lifetime
+    tkmk_r1cs_library *h = nullptr;
+    DeviceLibrary() = default;
+    DeviceLibrary(const DeviceLibrary &) = delete;
+    DeviceLibrary &operator=(const DeviceLibrary &) = delete;
+    ~DeviceLibrary() {
+        if (h) tkmk_r1cs_library_destroy(h);
+    }
+};
+inline bool is_infinity(const G1Affine &p) {
+    static const uint8_t zero[96] = {};
+    return std::memcmp(&p, zero, 96) == 0;
+}
+// e(lhs, q_lhs) = prod_k e(rhs[k].first, rhs[k].second), as ONE product e(lhs, q_lhs) prod e(-rhs, q) = 1
+inline bool pairing_equation(const G1Affine &lhs, const uint8_t *q_lhs, const std::vector<std::pair<G1Affine, const uint8_t *>> &rhs) {
+    std::vector<G1Affine> p{lhs};
+    std::vector<const uint8_t *> q{q_lhs};
+    for (const auto &t : rhs) {
+        pairing::G1Aff a;
+        if (!pairing::g1_decode(t.first, a)) throw Error("crs audit: an MSM result is not reduced");
+        p.push_back(pairing::g1_encode(pairing::g1_neg(a)));
+        q.push_back(t.second);
+    }
+    return pairing_product_is_one(p.data(), q.data(), p.size());
+}
+
+// Runs after membership, the G2 points, the anchors and both ratio checks have passed, with xy_powers (`grid`, plain records) still on
+// the device.  Fills rep.tables / rep.t_*; returns whether every table holds and, if not, leaves the first failure in rep.reason.
+// Throws for what is not a verdict on the CRS (an unreadable library file, a failed device call).
+inline bool audit_tables(const CrsPayload &crs, const SetupParams &sp, const std::string &lib_dir, DeviceVec<G1Affine> &grid, Report &rep) {
+    using clk = std::chrono::steady_clock;
+    auto since = [](clk::time_point t) { return std::chrono::duration<double>(clk::now() - t).count(); };
+    const size_t n = sp.n, s_max = sp.s_max, l = sp.l, l_free = sp.l_free, l_D = sp.l_D, m_D = sp.m_D, m_i = l_D - l;
+    const size_t rs_x = std::max(2 * n, 2 * m_i), rs_y = 2 * s_max, n_prv = m_D - l_D;
+    if (!is_pow2(n) || !is_pow2(s_max) || !is_pow2(m_i) || (l_free && !is_pow2(l_free))) throw Error("crs audit: n, s_max, m_I and l_free must be powers of two");
+    if (s_max < 4 || m_D < l_D || l_free > l || n + 2 >= rs_x || m_i + 1 >= rs_x) throw Error("crs audit: setup parameters out of range for the table checks");
+    if (grid.len() != rs_x * rs_y) throw Error("crs audit: the table checks need xy_powers on the device");
+    rep.tables.clear();
+    // what = "<section>: <what a failure means>"
+    auto verdict = [&](const char *name, uint64_t points, bool ok, const std::string &what) {
+        rep.tables.push_back(TableReport{name, points, ok});
+        const size_t cut = what.find(": ");
+        if (!ok && rep.reason.empty())
+            rep.reason = std::string("table ") + name + ": a record of " + what.substr(0, cut) + " is not what the circuit of " + lib_dir + " and sigma_2 determine" +
+                         what.substr(cut);
+        return ok;
+    };
+
+    // ---- the library: CSR on the device, and who owns each flattened wire ----
+    auto t0 = clk::now();
+    const SubcircuitLibrary library = SubcircuitLibrary::read_infos(lib_dir);
+    const size_t K = library.infos.size();
+    if (K == 0) throw Error("subcircuitInfo.json names no subcircuit");
+    std::vector<SubcircuitR1CS> r1cs(K);
+    for (size_t k = 0; k < K; k++) r1cs[k] = SubcircuitLibrary::read_r1cs(lib_dir, sp, library.infos[k], library.n_consts[k]);
+    const std::vector<std::vector<uint8_t>> own = flat_wire_owners(library.infos, r1cs, m_D);
+    DeviceLibrary dlib;
+    std::vector<size_t> w_off(K + 1, 0);
+    {
+        std::vector<uint32_t> n_rows(K), n_wires(K);
+        std::vector<const uint32_t *> rp(3 * K), wr(3 * K);
+        std::vector<const tkmk_fr *> cf(3 * K);
+        for (size_t k = 0; k < K; k++) {
+            n_rows[k] = r1cs[k].n_constraints, n_wires[k] = r1cs[k].n_wires;
+            w_off[k + 1] = w_off[k] + r1cs[k].n_wires;
+            for (int m = 0; m < 3; m++) rp[3 * k + m] = r1cs[k].row_ptr[m].data(), wr[3 * k + m] = r1cs[k].wire[m].data(), cf[3 * k + m] = r1cs[k].coeff[m].data();
+        }
+        check(tkmk_r1cs_library_create((uint32_t)K, n_rows.data(), n_wires.data(), rp.data(), wr.data(), cf.data(), &dlib.h), "tkmk_r1cs_library_create");
+    }
+    rep.t_library_s = since(t0);
+
+    // ---- the root of unity L_i, K_j, M_j are taken over: the one the CRS was made under ----
+    const G1Affine *xy = crs.g1(CrsPayload::XyPowers), *singles = crs.g1(CrsPayload::G1Singles);
+    try {
+        identify_crs_root(grid.ptr(), TKMK_BASES_PLAIN, singles[5], sp, true);
+    } catch (const Error &e) {
+        if (std::strncmp(e.what(), "the reference string's lagrange_KL", 34) != 0) throw;
+        if (rep.reason.empty()) rep.reason = std::string("the table checks need the root of unity the CRS was made under: ") + e.what();
+        return false;
+    }
+    init_ntt_domain_for_size(std::max(std::max(n, m_i), std::max(l_free, (size_t)1)) * s_max);
+
+    // ---- the scalars: a per flattened wire, b per placement column, 23 + 3 for the small tables, drawn after the file was fixed ----
+    t0 = clk::now();
+    const size_t n_rand = m_D + s_max + 26;
+    DeviceVec<ScalarField> rnd(n_rand);
+    check(tkmk_fr_random_device(draw_seed(), (uint64_t)rs_x * rs_y, n_rand, rnd.ptr(), nullptr), "tkmk_fr_random_device");
+    const std::vector<ScalarField> rnd_h = rnd.to_host();
+    const ScalarField *a_dev = rnd.ptr(), *b_dev = rnd.ptr() + m_D;
+    const ScalarField *a = rnd_h.data(), *c_small = rnd_h.data() + m_D + s_max, *d_chain = c_small + 23;
+
+    // per-kind weights of the three wire ranges, and the gamma table's column of each wire
+    enum { W_GAMMA = 0, W_ETA, W_DELTA };
+    auto g_of = [&](size_t f) { return f < sp.l_user_out ? 0 : f < sp.l_user ? 1 : f < l_free ? 2 : 3; };
+    std::vector<ScalarField> wt_h[3];
+    std::vector<uint8_t> col_h(w_off[K] ? w_off[K] : 1, 0);
+    for (auto &v : wt_h) v.assign(w_off[K] ? w_off[K] : 1, ScalarField{});
+    for (size_t k = 0; k < K; k++)
+        for (size_t j = 0; j < r1cs[k].n_wires; j++) {
+            const size_t f = library.infos[k].flattenMap[j];
+            if (f >= m_D) throw Error("subcircuitInfo.json: flattenMap entry outside the global wire range");
+            if (f < l) col_h[w_off[k] + j] = (uint8_t)g_of(f);
+            if (own[k][j]) wt_h[f < l ? W_GAMMA : f < l_D ? W_ETA : W_DELTA][w_off[k] + j] = a[f];
+        }
+    DeviceVec<ScalarField> wt_dev[3] = {DeviceVec<ScalarField>::from_host(wt_h[0]), DeviceVec<ScalarField>::from_host(wt_h[1]), DeviceVec<ScalarField>::from_host(wt_h[2])};
+    DeviceVec<uint8_t> col_dev = DeviceVec<uint8_t>::from_host(col_h);
+    auto kind_ptrs = [&](const ScalarField *base) {
+        std::vector<const tkmk_fr *> p(K);
+        for (size_t k = 0; k < K; k++) p[k] = base + w_off[k];
+        return p;
+    };
+    std::vector<const uint8_t *> col_ptrs(K);
+    for (size_t k = 0; k < K; k++) col_ptrs[k] = col_dev.ptr() + w_off[k];
+    rep.t_grids_s += since(t0);
+
+    const uint8_t *g2s = crs.bytes(CrsPayload::G2Points);
+    auto g2 = [&](int k) { return g2s + 192 * k; };   // 0 H, 1..4 [alpha^k]H, 5 [gamma]H, 6 [delta]H, 7 [eta]H, 8 [x]H, 9 [y]H
+    tkmk_msm_config cfg = tkmk_msm_default_config();
+    cfg.are_scalars_on_device = cfg.are_points_on_device = true;
+    // [sum coeff[h][i] x^h y^i]G over the xs x s_max corner of xy_powers
+    auto corner_job = [&](const DeviceVec<ScalarField> &coeffs, size_t xs) {
+        tkmk_msm_job_ex j{};
+        j.scalars = coeffs.ptr(), j.bases = grid.ptr(), j.msm_size = (int)(xs * s_max);
+        j.scalar_cols = j.scalar_stride = j.base_cols = (uint32_t)s_max, j.base_stride = (uint32_t)rs_y;
+        j.base_table_len = rs_x * rs_y;
+        return j;
+    };
+    auto coefficients = [&](const DeviceVec<ScalarField> &evals, size_t xs, size_t ys) {
+        DeviceVec<ScalarField> out(xs * ys);
+        check(tkmk_bintt(evals.ptr(), xs, ys, TKMK_NTT_INVERSE, nullptr, nullptr, true, nullptr, out.ptr()), "tkmk_bintt");
+        return out;
+    };
+    bool all = true;
+
+    // ---- eta and delta: T[j s_max + i] = s^-1 L_i(y) (o_{first + j}(x) [+ alpha^4 K_j(x)]) ----
+    auto outer_table = [&](const char *name, const char *what, CrsPayload::Section sec, int range, size_t first, size_t rows, bool with_k, int g2_s) {
+        if (rows == 0) return verdict(name, 0, true, what);   // vacuously true
+        auto t1 = clk::now();
+        const std::vector<const tkmk_fr *> wp = kind_ptrs(wt_dev[range].ptr());
+        DeviceVec<ScalarField> col[3] = {DeviceVec<ScalarField>(n), DeviceVec<ScalarField>(n), DeviceVec<ScalarField>(n)};
+        check(tkmk_r1cs_library_mix(dlib.h, wp.data(), nullptr, (uint32_t)n, 1, 1, col[0].ptr(), col[1].ptr(), col[2].ptr(), nullptr), "tkmk_r1cs_library_mix");
+        DeviceVec<ScalarField> coeff[3];
+        for (int m = 0; m < 3; m++) {
+            DeviceVec<ScalarField> ev(n * s_max);
+            check(tkmk_fr_outer(col[m].ptr(), (uint32_t)n, b_dev, (uint32_t)s_max, (uint32_t)s_max, ev.ptr(), nullptr), "tkmk_fr_outer");
+            coeff[m] = coefficients(ev, n, s_max);
+        }
+        DeviceVec<ScalarField> ab(rows * s_max), k_coeff;   // a_{first + j} b_i: the combination of the table, and the grid of the K term
+        check(tkmk_fr_outer(a_dev + first, (uint32_t)rows, b_dev, (uint32_t)s_max, (uint32_t)s_max, ab.ptr(), nullptr), "tkmk_fr_outer");
+        if (with_k) k_coeff = coefficients(ab, rows, s_max);
+        check(tkmk_device_synchronize(), "synchronize");
+        rep.t_grids_s += since(t1);
+        t1 = clk::now();
+        DeviceVec<G1Affine> table = crs.upload(sec);
+        tkmk_msm_job_ex jobs[5] = {};
+        jobs[0].scalars = ab.ptr(), jobs[0].bases = table.ptr(), jobs[0].msm_size = (int)(rows * s_max), jobs[0].base_table_len = rows * s_max;
+        for (int m = 0; m < 3; m++) jobs[1 + m] = corner_job(coeff[m], n);
+        if (with_k) jobs[4] = corner_job(k_coeff, rows);
+        tkmk_g1_projective sums[5];
+        check(tkmk_msm_multi_ex(jobs, with_k ? 5 : 4, &cfg, TKMK_BASES_PLAIN, sums), "tkmk_msm_multi_ex");
+        rep.t_msm_s += since(t1);
+        t1 = clk::now();
+        std::vector<std::pair<G1Affine, const uint8_t *>> rhs;
+        for (int m = 0; m < 3; m++) rhs.push_back({projective_to_affine(sums[1 + m]), g2(1 + m)});
+        if (with_k) rhs.push_back({projective_to_affine(sums[4]), g2(4)});
+        const bool ok = pairing_equation(projective_to_affine(sums[0]), g2(g2_s), rhs);
+        rep.t_pairing_s += since(t1);
+        return verdict(name, rows * s_max, ok, what);
+    };
+
+    // ---- gamma: T[j] = gamma^-1 (L_{g(j)}(y) o_j(x) + [j < l_free] M_j(x)) ----
+    auto gamma_table = [&]() {
+        const char *what = "gamma_inv_o_inst: a wrong or misplaced record, a CRS made for another library, or a wrong sigma_2.gamma";
+        if (l == 0) return verdict("gamma", 0, true, what);
+        auto t1 = clk::now();
+        const std::vector<const tkmk_fr *> wp = kind_ptrs(wt_dev[W_GAMMA].ptr());
+        DeviceVec<ScalarField> coeff[3];
+        {
+            DeviceVec<ScalarField> ev[3] = {DeviceVec<ScalarField>(n * s_max), DeviceVec<ScalarField>(n * s_max), DeviceVec<ScalarField>(n * s_max)};
+            for (auto &e : ev) check(tkmk_memset(e.ptr(), 0, n * s_max * sizeof(ScalarField)), "tkmk_memset");
+            check(tkmk_r1cs_library_mix(dlib.h, wp.data(), col_ptrs.data(), (uint32_t)n, 4, (uint32_t)s_max, ev[0].ptr(), ev[1].ptr(), ev[2].ptr(), nullptr),
+                  "tkmk_r1cs_library_mix");
+            for (int m = 0; m < 3; m++) coeff[m] = coefficients(ev[m], n, s_max);
+        }
+        DeviceVec<ScalarField> m_coeff;
+        if (l_free) {
+            m_coeff = DeviceVec<ScalarField>(l_free);
+            check(tkmk_bintt(a_dev, l_free, 1, TKMK_NTT_INVERSE, nullptr, nullptr, true, nullptr, m_coeff.ptr()), "tkmk_bintt");
+        }
+        check(tkmk_device_synchronize(), "synchronize");
+        rep.t_grids_s += since(t1);
+        t1 = clk::now();
+        DeviceVec<G1Affine> table = crs.upload(CrsPayload::GammaInvOInst);
+        tkmk_msm_job_ex jobs[5] = {};
+        jobs[0].scalars = a_dev, jobs[0].bases = table.ptr(), jobs[0].msm_size = (int)l, jobs[0].base_table_len = l;
+        for (int m = 0; m < 3; m++) jobs[1 + m] = corner_job(coeff[m], n);
+        if (l_free) {   // column 0 of xy_powers: [x^h]G
+            jobs[4].scalars = m_coeff.ptr(), jobs[4].bases = grid.ptr(), jobs[4].msm_size = (int)l_free;
+            jobs[4].base_cols = 1, jobs[4].base_stride = (uint32_t)rs_y, jobs[4].scalar_cols = 1, jobs[4].scalar_stride = 1;
+            jobs[4].base_table_len = rs_x * rs_y;
+        }
+        tkmk_g1_projective sums[5];
+        check(tkmk_msm_multi_ex(jobs, l_free ? 5 : 4, &cfg, TKMK_BASES_PLAIN, sums), "tkmk_msm_multi_ex");
+        rep.t_msm_s += since(t1);
+        t1 = clk::now();
+        std::vector<std::pair<G1Affine, const uint8_t *>> rhs;
+        for (int m = 0; m < 3; m++) rhs.push_back({projective_to_affine(sums[1 + m]), g2(1 + m)});
+        if (l_free) rhs.push_back({projective_to_affine(sums[4]), g2(0)});
+        const bool ok = pairing_equation(projective_to_affine(sums[0]), g2(5), rhs);
+        rep.t_pairing_s += since(t1);
+        return verdict("gamma", l, ok, what);
+    };
+    all &= gamma_table();
+    all &= outer_table("eta", "eta_inv_li_o_inter_alpha4_kj: a wrong or misplaced record, a CRS made for another library, or a wrong sigma_2.eta",
+                       CrsPayload::EtaInvLiOInterAlpha4Kj, W_ETA, l, m_i, true, 7);
+    all &= outer_table("delta", "delta_inv_li_o_prv: a wrong or misplaced record, a CRS made for another library, or a wrong sigma_2.delta",
+                       CrsPayload::DeltaInvLiOPrv, W_DELTA, l_D, n_prv, false, 6);
+
+    // ---- the small delta tables, the alpha chain and the single points: host arithmetic ----
+    t0 = clk::now();
+    auto pt = [&](const G1Affine &rec) {
+        pairing::G1Aff p;
+        if (!pairing::g1_decode(rec, p)) throw Error("crs audit: a record that passed membership is not reduced");
+        return p;
+    };
+    const G1Affine *xh = crs.g1(CrsPayload::DeltaInvAlphakXhTx), *xj = crs.g1(CrsPayload::DeltaInvAlpha4XjTx), *yi = crs.g1(CrsPayload::DeltaInvAlphakYiTy);
+    {
+        bool none_inf = true;
+        for (int k = 0; k < 9; k++) none_inf &= !is_infinity(xh[k]);
+        for (int k = 0; k < 2; k++) none_inf &= !is_infinity(xj[k]);
+        for (int k = 0; k < 12; k++) none_inf &= !is_infinity(yi[k]);
+        bool ok = none_inf;
+        if (ok) {
+            // c: [0, 9) for xh, [9, 11) for xj, [11, 23) for yi
+            std::vector<std::pair<ScalarField, pairing::G1Aff>> lhs;
+            for (int k = 0; k < 9; k++) lhs.push_back({c_small[k], pt(xh[k])});
+            for (int k = 0; k < 2; k++) lhs.push_back({c_small[9 + k], pt(xj[k])});
+            for (int k = 0; k < 12; k++) lhs.push_back({c_small[11 + k], pt(yi[k])});
+            auto diff = [&](std::vector<std::pair<ScalarField, pairing::G1Aff>> &t, const ScalarField &c, size_t hi, size_t lo) {   // c (xy[hi] - xy[lo])
+                t.push_back({c, pt(xy[hi])});
+                t.push_back({fr_neg(c), pt(xy[lo])});
+            };
+            std::vector<std::pair<G1Affine, const uint8_t *>> rhs;
+            for (int k = 1; k <= 4; k++) {
+                std::vector<std::pair<ScalarField, pairing::G1Aff>> t;
+                if (k <= 3)
+                    for (size_t h = 0; h < 3; h++) diff(t, c_small[3 * (k - 1) + h], (n + h) * rs_y, h * rs_y);        // x^h (x^n - 1)
+                else
+                    for (size_t j = 0; j < 2; j++) diff(t, c_small[9 + j], (m_i + j) * rs_y, j * rs_y);                  // x^j (x^m_I - 1)
+                for (size_t i = 0; i < 3; i++) diff(t, c_small[11 + 3 * (k - 1) + i], s_max + i, i);                     // y^i (y^s_max - 1)
+                rhs.push_back({pairing::g1_encode(pairing::g1_lincomb(t)), g2(k)});
+            }
+            ok = pairing_equation(pairing::g1_encode(pairing::g1_lincomb(lhs)), g2(6), rhs);
+        }
+        all &= verdict("delta_small", 23, ok,
+                       none_inf ? "delta_inv_alphak_xh_tx / delta_inv_alpha4_xj_tx / delta_inv_alphak_yi_ty: a wrong or misplaced record, or a wrong sigma_2.delta or sigma_2.alpha^k"
+                                : "delta_inv_alphak_xh_tx / delta_inv_alpha4_xj_tx / delta_inv_alphak_yi_ty: one is the point at infinity, which delta^-1 alpha^k t(x) never is");
+    }
+    {
+        std::vector<std::pair<ScalarField, pairing::G1Aff>> lo, hi;
+        for (int k = 1; k <= 3; k++) lo.push_back({d_chain[k - 1], pt(yi[3 * (k - 1)])}), hi.push_back({d_chain[k - 1], pt(yi[3 * k])});
+        const bool ok = pairing_equation(pairing::g1_encode(pairing::g1_lincomb(lo)), g2(1), {{pairing::g1_encode(pairing::g1_lincomb(hi)), g2(0)}});
+        all &= verdict("alpha_chain", 4, ok, "delta_inv_alphak_yi_ty along alpha: yi[3k] is not [alpha] yi[3(k-1)], so a record is misplaced or sigma_2.alpha .. alpha4 are not powers of one alpha");
+    }
+    {
+        const bool ok = pairing_equation(singles[3], g2(0), {{singles[0], g2(6)}}) && pairing_equation(singles[4], g2(0), {{singles[0], g2(7)}});
+        all &= verdict("singles", 2, ok, "sigma_1.delta / sigma_1.eta: they are not [delta]G and [eta]G for the delta and eta of sigma_2");
+    }
+    rep.t_pairing_s += since(t0);
+    return all;
+}
+
 // The audit of one loaded payload.  Returns rep.ok; throws for what is not a verdict on the CRS (sizes that do not match setupParams.json,
 // no device, a failed device call).  Everything runs on the default stream.
-inline bool audit_payload(const CrsPayload &crs, const SetupParams &sp, Report &rep) {
+inline bool audit_payload(const CrsPayload &crs, const SetupParams &sp, Report &rep, bool circuit = false, const std::string &lib_dir = std::string()) {
     using clk = std::chrono::steady_clock;
     auto since = [](clk::time_point t) { return std::chrono::duration<double>(clk::now() - t).count(); };
     const auto t_all = clk::now();
@@ -213,7 +520,7 @@ inline bool audit_payload(const CrsPayload &crs, const SetupParams &sp, Report &
         check(tkmk_msm_multi_ex(jobs, 4, &cfg, TKMK_BASES_PLAIN, sums), "tkmk_msm_multi_ex");
         rep.msm_s = since(t0);
     }
-    grid = DeviceVec<G1Affine>();
+    if (!circuit) grid = DeviceVec<G1Affine>();   // the table checks read xy_powers again
     {
         const auto t0 = clk::now();
         const uint8_t *g2s = crs.bytes(CrsPayload::G2Points), *H = g2s, *xH = g2s + 192 * 8, *yH = g2s + 192 * 9;
@@ -231,22 +538,32 @@ inline bool audit_payload(const CrsPayload &crs, const SetupParams &sp, Report &
     if (!rep.ratio_y) fail("xy_powers is not a table of powers along Y: sum rho P[a][b+1] != [y] sum rho P[a][b] for a random rho (a record is in the wrong place, or sigma_2.y is not [y]H)");
     if (!rep.ratio_x) fail("xy_powers is not a table of powers along X: sum rho P[a+1][b] != [x] sum rho P[a][b] for a random rho (a record is in the wrong place, or sigma_2.x is not [x]H)");
     rep.ok = rep.anchors == 1 && rep.ratio_y == 1 && rep.ratio_x == 1;
+    if (circuit && rep.ok) {   // the table checks rest on xy_powers being right
+        rep.circuit = audit_tables(crs, sp, lib_dir, grid, rep) ? 1 : 0;
+        if (!rep.circuit) rep.ok = false;
+        grid = DeviceVec<G1Affine>();
+    }
     return finish();
 }
 
-// <lib>/setupParams.json + <crs>/combined_sigma.{tkcrs, rkyv}; an unreadable file throws
-inline bool audit_files(const std::string &lib_dir, const std::string &crs_dir, Report &rep, std::string *container = nullptr) {
+// <lib>/setupParams.json + <crs>/combined_sigma.{tkcrs, rkyv}, with `circuit` also <lib>/subcircuitInfo.json and <lib>/r1cs/; an unreadable
+// file throws
+inline bool audit_files(const std::string &lib_dir, const std::string &crs_dir, Report &rep, std::string *container = nullptr, bool circuit = false) {
     const SetupParams sp = read_setup_params(lib_dir);
     if (sp.l_D < sp.l) throw Error("Invalid setup params: l_D must be >= l.");
     const CrsPayload crs = load_combined_sigma(crs_dir, sp);
     if (container) *container = crs.container;
-    return audit_payload(crs, sp, rep);
+    return audit_payload(crs, sp, rep, circuit, lib_dir);
 }
 
-// TKMK_PROVER_CHECK_CRS=1 (tkmk_prover_open): unset, empty or "0" = off
+// TKMK_PROVER_CHECK_CRS=1 (tkmk_prover_open): unset, empty or "0" = off; "2" = with the table checks against the circuit
 inline bool requested_at_open() {
     const char *e = std::getenv("TKMK_PROVER_CHECK_CRS");
     return e && *e && std::strcmp(e, "0") != 0;
+}
+inline bool circuit_requested_at_open() {
+    const char *e = std::getenv("TKMK_PROVER_CHECK_CRS");
+    return e && std::strcmp(e, "2") == 0;
 }
 
 }  // namespace crs_audit

@@ -71,8 +71,7 @@ inline std::vector<ScalarField> evaled_qap_mixture(const std::string &qap_path, 
     std::vector<ScalarField> o_vec(sp.m_D);
     for (size_t s = 0; s < infos.size(); s++) {
         const SubcircuitInfo &info = infos[s];
-        R1csBinary b = R1csBinary::read(qap_path + "/r1cs/subcircuit" + std::to_string(info.id) + ".r1cs");
-        SubcircuitR1CS r = SubcircuitR1CS::from_r1cs_sparse_only(b, sp, info, n_consts.at(s));
+        SubcircuitR1CS r = SubcircuitLibrary::read_r1cs(qap_path, sp, info, n_consts.at(s));
         std::vector<ScalarField> o(r.n_wires);
         for (int m = 0; m < 3; m++) {
             size_t nnz = r.wire[m].size();
@@ -101,6 +100,7 @@ inline std::vector<ScalarField> evaled_qap_mixture(const std::string &qap_path, 
             for (uint32_t j = 0; j < r.n_wires; j++)
                 if (!fr_is_zero(h[j])) o[j] = fr_add(o[j], fr_mul(alpha[m], h[j]));
         }
+        // a flattened wire keeps the LAST non-zero o_j written to it: the rule flat_wire_owners (host/tkmk_witness.hpp) restates for the audit
         for (uint32_t j = 0; j < r.n_wires; j++)
             if (!fr_is_zero(o[j])) o_vec.at(info.flattenMap.at(j)) = o[j];
     }

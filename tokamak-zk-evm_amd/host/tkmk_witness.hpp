@@ -2,10 +2,12 @@
 //   R1csBinary / SubcircuitR1CS::from_r1cs_sparse_only   libs/src/iotools/mod.rs:505-760   (iden3 .r1cs v1, same validations)
 //   read_R1CS_gen_uvwXY                                  libs/src/iotools/mod.rs:1287-1420 (sparse rows x placement variables on the device)
 //   gen_bXY, Instance::gen_a_free_X                      libs/src/polynomial_structures/mod.rs:104-162
-// Include after tkmk_protocol.hpp (PlacementVariables, SubcircuitInfo, SetupParams).  JSON parsing stays with the caller.
+//   SubcircuitLibrary, flat_wire_owners                  the library directory as the setup and the CRS audit read it
+// Include after tkmk_protocol.hpp (PlacementVariables, SubcircuitInfo, SetupParams).  JSON parsing of the witness stays with the caller.
 #pragma once
 #include <map>
 
+#include "tkmk_json.hpp"
 #include "tkmk_protocol.hpp"
 
 namespace tkmk {
@@ -152,6 +154,63 @@ struct SubcircuitR1CS {
         return r;
     }
 };
+
+// The subcircuit library of a directory as the trusted setup and the CRS audit read it: <lib>/subcircuitInfo.json in file order, and per
+// entry <lib>/r1cs/subcircuit{id}.r1cs.  A missing or malformed file throws.
+struct SubcircuitLibrary {
+    std::vector<SubcircuitInfo> infos;
+    std::vector<size_t> n_consts;
+
+    static SubcircuitLibrary read_infos(const std::string &lib_dir) {
+        SubcircuitLibrary lib;
+        const json::Value jinfo = json::read_file(lib_dir + "/subcircuitInfo.json");
+        for (const json::Value &e : jinfo.items()) {
+            SubcircuitInfo si;
+            si.id = e.at("id").as_size();
+            si.name = e.at("name").as_string();
+            si.Nwires = e.at("Nwires").as_size();
+            si.Out_idx = {e.at("Out_idx").items().at(0).as_size(), e.at("Out_idx").items().at(1).as_size()};
+            si.In_idx = {e.at("In_idx").items().at(0).as_size(), e.at("In_idx").items().at(1).as_size()};
+            for (const json::Value &g : e.at("flattenMap").items()) si.flattenMap.push_back(g.as_size());
+            lib.infos.push_back(std::move(si));
+            lib.n_consts.push_back(e.at("Nconsts").as_size());
+        }
+        return lib;
+    }
+    // entry s of the library (not subcircuit id s)
+    static SubcircuitR1CS read_r1cs(const std::string &lib_dir, const SetupParams &sp, const SubcircuitInfo &info, size_t n_consts) {
+        R1csBinary b = R1csBinary::read(lib_dir + "/r1cs/subcircuit" + std::to_string(info.id) + ".r1cs");
+        return SubcircuitR1CS::from_r1cs_sparse_only(b, sp, info, n_consts);
+    }
+};
+
+// Which (entry s, local wire j) OWNS the flattened wire flattenMap[j]?  The setup's o_vec (evaled_qap_mixture, host/tkmk_setup.hpp) is
+// written entry by entry, wire by wire, and only where o_j is non-zero, so a flattened index that several pairs map to keeps the value of
+// the LAST pair, in that order, whose column of A, B or C holds an entry (a column with entries evaluates to zero at a random tau_x
+// only with probability ~ n / r).  own[s][j] = 1 for that pair, 0 for every other: the CRS audit weights wires by it.
+inline std::vector<std::vector<uint8_t>> flat_wire_owners(const std::vector<SubcircuitInfo> &infos, const std::vector<SubcircuitR1CS> &r1cs, size_t m_D) {
+    if (infos.size() != r1cs.size()) throw Error("flat_wire_owners: one constraint system per library entry");
+    std::vector<std::vector<uint8_t>> own(infos.size());
+    std::vector<std::pair<uint32_t, uint32_t>> last(m_D, {UINT32_MAX, 0u});
+    for (size_t s = 0; s < infos.size(); s++) {
+        const SubcircuitR1CS &r = r1cs[s];
+        if (infos[s].flattenMap.size() != r.n_wires) throw Error("subcircuitInfo.json: flattenMap length differs from Nwires for subcircuit " + std::to_string(infos[s].id));
+        std::vector<uint8_t> used(r.n_wires, 0);
+        for (int m = 0; m < 3; m++)
+            for (size_t k = 0; k < r.wire[m].size(); k++)
+                if (!fr_is_zero(r.coeff[m][k])) used[r.wire[m][k]] = 1;
+        for (uint32_t j = 0; j < r.n_wires; j++) {
+            if (!used[j]) continue;
+            const size_t f = infos[s].flattenMap[j];
+            if (f >= m_D) throw Error("subcircuitInfo.json: flattenMap entry outside the global wire range");
+            last[f] = {(uint32_t)s, j};
+        }
+        own[s].assign(r.n_wires, 0);
+    }
+    for (const auto &p : last)
+        if (p.first != UINT32_MAX) own[p.first][p.second] = 1;
+    return own;
+}
 
 // read_R1CS_gen_uvwXY: r1cs_of(subcircuit id) supplies the parsed constraint system of every used subcircuit
 template <class R1csOf>

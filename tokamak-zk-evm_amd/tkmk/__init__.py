@@ -98,6 +98,7 @@ SYMBOLS = [
     "tkmk_poly_place", "tkmk_poly_scale_coeffs", "tkmk_poly_mul_x_minus_one_evals", "tkmk_poly_mul_ones_x", "tkmk_poly_expr_eval", "tkmk_poly_expr_eval_views", "tkmk_poly_expr_eval_views_slab", "tkmk_poly_eval_x", "tkmk_poly_eval_y", "tkmk_poly_eval",
     "tkmk_poly_div_by_vanishing_opt", "tkmk_poly_div_by_ruffini", "tkmk_r1cs_eval_rows",
     "tkmk_msm_multi_ex", "bls12_381_msm_convert_bases", "tkmk_r1cs_library_create", "tkmk_r1cs_library_destroy", "tkmk_r1cs_library_eval",
+    "tkmk_r1cs_library_mix", "tkmk_fr_outer",
     "tkmk_witness_route", "tkmk_fr_scatter_table", "tkmk_msm_set_pipeline_streams", "tkmk_msm_get_pipeline_streams", "tkmk_host_malloc", "tkmk_host_free", "tkmk_stats_reset", "tkmk_stats_get",
     "bls12_381_ntt_domain_size", "bn254_ntt_domain_size", "tkmk_poly_lincomb", "tkmk_bintt_padded", "tkmk_diag_device_switch", "tkmk_diag_gather_probe",
     "bls12_381_get_root_of_unity_with_generator", "tkmk_ntt_root_generator", "tkmk_ntt_set_root_generator", "tkmk_poly_geometric_grid", "tkmk_crs_identify_root", "tkmk_g1_check",
@@ -754,6 +755,32 @@ def gather_rows_device(src, row_bytes, idx, out=None):
     _check(lib().tkmk_gather_rows_device(_p(src), ctypes.c_uint32(row_bytes), _p(idx), ctypes.c_uint64(n), _p(out), None),
            "tkmk_gather_rows_device")
     return out
+
+
+def fr_outer(col, rows, row, cols, out_stride=None, out=None):
+    """tkmk_fr_outer: out[j * out_stride + i] = col[j] * row[i] (DeviceBuffers of plain Fr; out_stride defaults to cols; the padding of a
+    caller's `out` is not touched)"""
+    out_stride = cols if out_stride is None else out_stride
+    out = DeviceBuffer(32 * rows * out_stride) if out is None else out
+    _check(lib().tkmk_fr_outer(_p(col), ctypes.c_uint32(rows), _p(row), ctypes.c_uint32(cols), ctypes.c_uint32(out_stride), _p(out), None), "tkmk_fr_outer")
+    return out
+
+
+def r1cs_library_mix(library, weights, cols, n, n_cols, out_stride=None, outs=None):
+    """tkmk_r1cs_library_mix over a tkmk.witness.R1csLibrary: weights = one DeviceBuffer of n_wires plain Fr per kind, cols = None or per kind
+    None / a DeviceBuffer of n_wires bytes (the output column of each wire) -> (u, v, w) DeviceBuffers, n rows of out_stride elements of
+    which the first n_cols are written: u[c][g] = sum over kinds and over the entries of row c of A whose wire routes to g of
+    coeff * weight (v, w from B, C)"""
+    out_stride = n_cols if out_stride is None else out_stride
+    k = len(weights)
+    wp = (ctypes.c_void_p * max(k, 1))(*[w.ptr if w is not None else None for w in weights])
+    cp = None
+    if cols is not None:
+        cp = (ctypes.c_void_p * max(k, 1))(*[c.ptr if c is not None else None for c in cols])
+    outs = [DeviceBuffer(32 * n * out_stride) for _ in range(3)] if outs is None else outs
+    _check(lib().tkmk_r1cs_library_mix(library._h, wp, cp, ctypes.c_uint32(n), ctypes.c_uint32(n_cols), ctypes.c_uint32(out_stride), _p(outs[0]), _p(outs[1]),
+                                       _p(outs[2]), None), "tkmk_r1cs_library_mix")
+    return tuple(outs)
 
 
 class ExprInstr(ctypes.Structure):

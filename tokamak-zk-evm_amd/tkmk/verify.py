@@ -18,6 +18,7 @@ def _lib(testing=False):
         l.tkmk_verify_files.argtypes = [ctypes.c_char_p] * 5 + [ctypes.c_uint32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p)]
         l.tkmk_prover_verify.argtypes = [ctypes.c_void_p] + [ctypes.c_char_p] * 3 + [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p)]
         l.tkmk_crs_audit_files.argtypes = [ctypes.c_char_p] * 2 + [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p)]
+        l.tkmk_crs_audit_circuit_files.argtypes = l.tkmk_crs_audit_files.argtypes
         l._tkmk_verify_bound = True
     return l
 
@@ -77,17 +78,22 @@ def verify_files(subcircuit_library_dir, crs_dir, synthesizer_dir, preprocess_di
     return ok.value == 1, _take_report(l, doc)
 
 
-def crs_audit(subcircuit_library_dir, crs_dir, testing=False):
+def crs_audit(subcircuit_library_dir, crs_dir, testing=False, circuit=False):
     """-> (ok, report): tkmk_crs_audit_files — is the reference string <crs_dir>/combined_sigma.{tkcrs, rkyv} well formed for the circuit of
     <subcircuit_library_dir>: membership of every G1 record on the device (tkmk_g1_check) and of the ten G2 points on the host, the anchors,
     and the power structure of xy_powers by four MSMs and two pairing products.  report = {"ok", "reason", "sections": [{"name", "points",
     "infinity", "noncanonical", "off_curve", "not_in_subgroup", "first_bad"}], "g2", "anchors", "ratio_y", "ratio_x", "seconds"}.  Needs a
-    device; service.ProverError for unreadable input.  testing=True: libtkmk_prover_testing.so, which honours TKMK_CRS_AUDIT_SEED."""
+    device; service.ProverError for unreadable input.  testing=True: libtkmk_prover_testing.so, which honours TKMK_CRS_AUDIT_SEED.
+    circuit=True: tkmk_crs_audit_circuit_files — after all of that, the gamma / eta / delta tables, the small delta tables and the single
+    points against the circuit (<lib>/subcircuitInfo.json, <lib>/r1cs/) and sigma_2; the report's "circuit" is then the verdict of those
+    checks, "tables" = [{"name", "points", "ok"}] for gamma, eta, delta, delta_small, alpha_chain, singles and "table_seconds" their
+    times (all three are None without it)."""
     l = _lib(testing)
     ok, doc = ctypes.c_int(-1), ctypes.c_void_p()
-    code = l.tkmk_crs_audit_files(os.fsencode(subcircuit_library_dir), os.fsencode(crs_dir), ctypes.byref(ok), ctypes.byref(doc))
+    name = "tkmk_crs_audit_circuit_files" if circuit else "tkmk_crs_audit_files"
+    code = getattr(l, name)(os.fsencode(subcircuit_library_dir), os.fsencode(crs_dir), ctypes.byref(ok), ctypes.byref(doc))
     if code != 0:
-        raise service.ProverError(code, "tkmk_crs_audit_files", testing)
+        raise service.ProverError(code, name, testing)
     return ok.value == 1, _take_report(l, doc)
 
 
