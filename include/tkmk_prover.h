@@ -139,6 +139,44 @@ tkmk_error tkmk_verify_files(const char *subcircuit_library_dir, const char *crs
 tkmk_error tkmk_prover_verify(tkmk_prover *p, const char *synthesizer_dir, const char *preprocess_dir, const char *proof_dir, int *ok,
                               char **report_json_out);
 
+/* ---- Batch verification: n proofs of ONE circuit against ONE reference string (verify_batch of host/tkmk_verify.hpp) ----
+ * Every proof is checked against the same ten G2 points and every G1 input of its ten pairs is a linear combination of named points, so
+ * with fresh random weights r_k the product over a set of proofs collapses to ten pairs again: prod_j e(sum_k r_k P_{k,j}, Q_j) = 1.  A
+ * batch of honest proofs costs ONE product of ten pairings, ten multi-scalar multiplications over about 22 n points and one membership
+ * pass, instead of n products.
+ *   verdicts    PER PROOF, never per batch: ok_each[k] = 1 / 0 equals what tkmk_verify_files says for item k alone, *ok_all = 1 iff all are
+ *               1.  If the fold of all items fails, the set is halved and re-folded until the false items stand alone: at most
+ *               1 + 2 b ceil(log2 n) products for b false items; the report's "products" is the count.
+ *   weights     r_k in [1, 2^128) from getrandom(), drawn after every input is loaded, new for every fold (re-folds included), never
+ *               derived from a counter or a seed expansion: a set holding a false proof passes a fold with probability <= 2^-128.
+ *   membership  is never folded (E(Fp) has a cofactor; a random combination does not see a small-order component): every distinct G1
+ *               record is checked, an item with a bad one is false with the single verifier's reason and enters no fold.  Records shared
+ *               by many items (G, sigma_1.x, sigma_1.y, lagrange_KL; s0, s1, O_pub_fix of items with the same preprocess) are checked
+ *               once.  Sigma2 is checked once; an all-zero Sigma2, a bad G2 point or one at infinity makes every item false with that reason.
+ *   route       the caller's choice, no hidden size threshold.  TKMK_VERIFY_ROUTE_HOST: pure host work on TKMK_HOST_THREADS threads, no
+ *               device call.  TKMK_VERIFY_ROUTE_DEVICE: the records are uploaded once, ONE tkmk_g1_check call does the membership pass and
+ *               ONE tkmk_msm_multi_ex call per fold the ten sums (host/tkmk_verify_device.hpp); the pairing stays on the host.  It runs on
+ *               the default stream in its own buffers, takes turns with the prover contexts of the process, and reads and changes no
+ *               library or context state (NTT domain, generator in effect, commit tables).  Without a device: TKMK_ERR_NO_DEVICE.  For
+ *               one or a few items the device route is SLOWER than the host route.
+ *   errors      n = 0 is TKMK_ERR_INVALID_ARGUMENT (a vacuous "all true" does not exist); a document that cannot be read or parsed is an
+ *               error whose message names the item index and the file, and no verdict is given.
+ * report_json_out (optional, tkmk_prover_free_string): {"generator", "ok", "n", "route": "host" | "device", "products", "items": [one
+ * report of tkmk_verify_files per item], "seconds": {"parse", "membership", "fold", "pairings", "total"}}.
+ * NOT covered: batches across different reference strings or circuits, BN254, a device route for sharded contexts. */
+typedef struct {
+    const char *synthesizer_dir, *preprocess_dir, *proof_dir;
+} tkmk_verify_item;
+#define TKMK_VERIFY_ROUTE_HOST 0
+#define TKMK_VERIFY_ROUTE_DEVICE 1
+tkmk_error tkmk_verify_batch_files(const char *subcircuit_library_dir, const char *crs_dir, const tkmk_verify_item *items, size_t n,
+                                   uint32_t root_generator, int route, uint8_t *ok_each /* n */, int *ok_all, char **report_json_out);
+/* The same against the context's own reference string and generator (as tkmk_prover_verify); the Sigma2 check is made once per context and
+ * kept.  TKMK_VERIFY_ROUTE_DEVICE on a context from tkmk_prover_open_sharded is TKMK_ERR_INVALID_ARGUMENT: sharded ranks keep the host
+ * route, which needs no collective — every rank may call it. */
+tkmk_error tkmk_prover_verify_batch(tkmk_prover *p, const tkmk_verify_item *items, size_t n, int route, uint8_t *ok_each, int *ok_all,
+                                    char **report_json_out);
+
 
 /* ---- The audit of a reference string (host/tkmk_crs_audit.hpp; needs a device) ----
  * Reads <lib>/setupParams.json and <crs>/combined_sigma.tkcrs or .rkyv (as tkmk_prover_open does) and decides whether the CRS is well

@@ -1,7 +1,8 @@
 // prover_abi.cpp — libtkmk_prover.so: the C ABI of include/tkmk_prover.h over host/tkmk_service.hpp (ProverContext).
 // Built twice: libtkmk_prover.so (production: blinding scalars always from getrandom(), a testing_mixer_json argument is refused)
 // and, with -DTKMK_TESTING_MODE, libtkmk_prover_testing.so for the differential tests (the reference's `testing-mode` feature).
-// Both carry the verifier's three entries (host/tkmk_verify.hpp, host/tkmk_pairing.hpp): pure host work, no device call.
+// Both carry the verifier's entries (host/tkmk_verify.hpp, host/tkmk_pairing.hpp): pure host work, no device call — except the device route
+// of the two batch entries (host/tkmk_verify_device.hpp), which the caller asks for.
 #include <dlfcn.h>
 
 #include <cstdlib>
@@ -14,11 +15,14 @@
 #include "tkmk_crs_load.hpp"
 #include "tkmk_service.hpp"
 #include "tkmk_verify.hpp"
+#include "tkmk_verify_device.hpp"
 
 using namespace tkmk;
 
 struct tkmk_prover {
     std::unique_ptr<ProverContext> ctx;
+    std::mutex sigma2_mu;
+    std::unique_ptr<verify::Sigma2> sigma2;   // the checked G2 side of the context's reference string (tkmk_prover_verify_batch), made on first use
 };
 
 static thread_local std::string g_last_error;
@@ -265,5 +269,69 @@ TKP_API tkmk_error tkmk_prover_verify(tkmk_prover *p, const char *synthesizer_di
         verify::Report rep;
         const bool verdict = verify::verify_loaded(in, c.root_generator, rep);   // the generator the context identified at open
         hand_over(verdict, rep, ok, report_json_out);
+    });
+}
+
+// ---- batch verification (verify_batch of host/tkmk_verify.hpp; the device route is host/tkmk_verify_device.hpp) ----
+// route HOST: pure host work, as the three entries above.  route DEVICE: upload, one tkmk_g1_check, one tkmk_msm_multi_ex per fold on the
+// default stream, so it takes the unsharded contexts' turn, as the audit does.
+static void batch_entry(const char *entry, const verify::Inputs &shared, const tkmk_verify_item *items, size_t n, uint32_t generator, int route,
+                        std::unique_ptr<verify::Sigma2> *sigma2_cache, uint8_t *ok_each, int *ok_all, char **report_json_out) {
+    if (n == 0) throw Error(std::string(entry) + ": an empty batch has no verdict (n must be at least 1)");
+    if (route != TKMK_VERIFY_ROUTE_HOST && route != TKMK_VERIFY_ROUTE_DEVICE) throw Error(std::string(entry) + ": unknown route");
+    std::vector<verify::BatchItem> list(n);
+    for (size_t k = 0; k < n; k++) {
+        if (!items[k].synthesizer_dir || !items[k].preprocess_dir || !items[k].proof_dir) throw Error(TKMK_ERR_INVALID_POINTER, std::string(entry) + ": item " + std::to_string(k));
+        list[k] = {items[k].synthesizer_dir, items[k].preprocess_dir, items[k].proof_dir};
+    }
+    verify::BatchReport rep;
+    if (route == TKMK_VERIFY_ROUTE_DEVICE) {
+        int ndev = 0;
+        if (tkmk_device_count(&ndev) != TKMK_SUCCESS || ndev < 1) throw Error(TKMK_ERR_NO_DEVICE, std::string(entry) + ": TKMK_VERIFY_ROUTE_DEVICE needs a HIP device (the host route does not)");
+        DefaultStreamTurn turn(false);
+        verify::DeviceFolder folder;
+        verify::verify_batch(shared, list, generator, folder, rep, sigma2_cache);
+    } else {
+        verify::HostFolder folder;
+        verify::verify_batch(shared, list, generator, folder, rep, sigma2_cache);
+    }
+    for (size_t k = 0; k < n; k++) ok_each[k] = rep.items[k].ok ? 1 : 0;
+    if (report_json_out) *report_json_out = dup_string(rep.to_json());
+    *ok_all = rep.ok ? 1 : 0;
+}
+
+TKP_API tkmk_error tkmk_verify_batch_files(const char *subcircuit_library_dir, const char *crs_dir, const tkmk_verify_item *items, size_t n, uint32_t root_generator,
+                                           int route, uint8_t *ok_each, int *ok_all, char **report_json_out) {
+    if (!subcircuit_library_dir || !crs_dir || !ok_all || (n && (!items || !ok_each))) return TKMK_ERR_INVALID_POINTER;
+    *ok_all = 0;
+    if (n) std::memset(ok_each, 0, n);
+    if (report_json_out) *report_json_out = nullptr;
+    return guarded([&] {
+        if (n == 0) throw Error("tkmk_verify_batch_files: an empty batch has no verdict (n must be at least 1)");
+        verify::Inputs shared;
+        shared.sp = verify::read_shape(subcircuit_library_dir);
+        verify::validate_shape(shared.sp);
+        verify::read_sigma_verify(crs_dir, shared);
+        batch_entry("tkmk_verify_batch_files", shared, items, n, root_generator, route, nullptr, ok_each, ok_all, report_json_out);
+    });
+}
+
+TKP_API tkmk_error tkmk_prover_verify_batch(tkmk_prover *p, const tkmk_verify_item *items, size_t n, int route, uint8_t *ok_each, int *ok_all, char **report_json_out) {
+    if (!p || !ok_all || (n && (!items || !ok_each))) return TKMK_ERR_INVALID_POINTER;
+    *ok_all = 0;
+    if (n) std::memset(ok_each, 0, n);
+    if (report_json_out) *report_json_out = nullptr;
+    return guarded([&] {
+        const ProverContext &c = *p->ctx;
+        if (route == TKMK_VERIFY_ROUTE_DEVICE && c.link)
+            throw Error("tkmk_prover_verify_batch: TKMK_VERIFY_ROUTE_DEVICE is not available on a sharded context (its ranks keep the host route, which needs no collective)");
+        verify::Inputs shared;
+        shared.sp.n = c.sp.n, shared.sp.l = c.sp.l, shared.sp.l_D = c.sp.l_D, shared.sp.s_max = c.sp.s_max, shared.sp.l_user = c.sp.l_user, shared.sp.l_free = c.sp.l_free;
+        const auto &s = c.sigma->g1_singles;
+        shared.pt[verify::CRS_G] = s[0], shared.pt[verify::CRS_X] = s[1], shared.pt[verify::CRS_Y] = s[2], shared.pt[verify::CRS_KL] = s[5];
+        for (int k = 0; k < verify::G2Count; k++) std::memcpy(shared.g2[k].data(), c.sigma->g2_points.data() + 192 * k, 192);
+        shared.crs_label = c.crs_source;
+        std::lock_guard<std::mutex> lk(p->sigma2_mu);   // the Sigma2 check of this context's reference string: once per context
+        batch_entry("tkmk_prover_verify_batch", shared, items, n, c.root_generator, route, &p->sigma2, ok_each, ok_all, report_json_out);
     });
 }

@@ -21,8 +21,13 @@
 #include <sys/random.h>
 
 #include <array>
+#include <atomic>
 #include <fstream>
+#include <functional>
+#include <map>
+#include <memory>
 
+#include "tkmk_fastparse.hpp"
 #include "tkmk_json.hpp"
 #include "tkmk_pairing.hpp"
 #include "tkmk_transcript.hpp"
@@ -299,33 +304,47 @@ struct LC {   // a linear combination of the named G1 points
     }
 };
 
-// Verifier::verify_snark.  kappa2 = nullptr: fresh randomness.  Returns rep.ok; throws only for invalid setup parameters / generator.
-inline bool verify_loaded(const Inputs &in, uint32_t explicit_generator, Report &rep, const ScalarField *kappa2_in = nullptr) {
-    rep = Report{};
-    rep.generator = generator_in_effect(explicit_generator);
-    validate_shape(in.sp);
-    if (in.a_pub.size() != in.sp.l_free) throw Error("instance.json: expected l_free public inputs");
-    auto refuse = [&](const std::string &why) {
-        rep.ok = false, rep.reason = why;
-        return false;
-    };
-    // Sigma2 first: an all-zero G2 set would make every pairing 1
+// ---- Verifier::verify_snark in three parts: Sigma2, the per-proof part (the ten slot combinations), the deciding part ----
+// The ten pairs of the product, in its order: slot j is a combination of that proof's named points and pairs with slot_g2(j) of Sigma2.
+//   0 lhs + aux   1 B   2 U   3 V   4 W   5 -(O_pub_fix + O_pub_free)   6 -O_mid   7 -O_prv   8 -aux_x   9 -aux_y
+constexpr int kSlots = 10;
+inline int slot_g2(int j) {
+    static const int g2_of[kSlots] = {H, Alpha4, Alpha, Alpha2, Alpha3, Gamma, Eta, Delta, X2, Y2};
+    return g2_of[j];
+}
+struct Combination {   // what the per-proof part yields beside the challenges and a_eval of the report
+    ScalarField kappa2{};
+    std::array<LC, kSlots> slot{};
+};
+struct Sigma2 {   // the checked G2 side of a reference string: reason non-empty = refused (q is then not to be used)
+    std::string reason;
+    g2h::Affine q[G2Count];
+};
+// Sigma2 first: an all-zero G2 set would make every pairing 1
+inline void check_sigma2(const Inputs &in, Sigma2 &out) {
+    out.reason.clear();
     bool any_g2 = false;
     for (const auto &r : in.g2)
         for (uint8_t b : r) any_g2 |= b != 0;
-    if (!any_g2) return refuse(in.crs_label + " holds no Sigma2 (all-zero G2 points): every pairing would be 1 and the check vacuous");
-    g2h::Affine q[G2Count];
+    if (!any_g2) {
+        out.reason = in.crs_label + " holds no Sigma2 (all-zero G2 points): every pairing would be 1 and the check vacuous";
+        return;
+    }
     for (int k = 0; k < G2Count; k++) {
         const std::string who = in.crs_label + ": " + (k == H ? std::string("H") : std::string("sigma_2.") + g2_name(k));
-        const char *why = pairing::g2_check(in.g2[k].data(), q[k]);
-        if (*why) return refuse(who + " " + why);
-        if (q[k].inf) return refuse(who + " is the point at infinity");
+        const char *why = pairing::g2_check(in.g2[k].data(), out.q[k]);
+        if (*why) out.reason = who + " " + why;
+        else if (out.q[k].inf) out.reason = who + " is the point at infinity";
+        if (!out.reason.empty()) return;
     }
-    G1Aff pts[PtCount];
-    for (int i = 0; i < PtCount; i++) {
-        const char *why = pairing::g1_check(in.pt[i], pts[i]);
-        if (*why) return refuse((i < kProofPoints ? std::string("proof.json") : i < kProofPoints + kPrePoints ? std::string("preprocess.json") : in.crs_label) + ": " + pt_name(i) + " " + why);
-    }
+}
+// the reason of a G1 point that failed its checks: the document it came from, its name, `why` of pairing::g1_check
+inline std::string g1_reason(const Inputs &in, int i, const char *why) {
+    return (i < kProofPoints ? std::string("proof.json") : i < kProofPoints + kPrePoints ? std::string("preprocess.json") : in.crs_label) + ": " + pt_name(i) + " " + why;
+}
+// The per-proof part: transcript, kappa2 (nullptr: fresh randomness), a_pub(chi), the ten slot combinations.  Fills the challenges and
+// a_eval of rep (rep.generator is read).  Needs no point to be valid: it reads the records' bytes only.
+inline Combination combine(const Inputs &in, Report &rep, const ScalarField *kappa2_in = nullptr) {
     // Verifier::collect_challenges (verify-rust/src/lib.rs:98-117)
     TranscriptManager tm;
     tm.add_proof0(in.pt[U], in.pt[V], in.pt[W], in.pt[Q_AX], in.pt[Q_AY], in.pt[B]);
@@ -366,17 +385,38 @@ inline bool verify_loaded(const Inputs &in, uint32_t explicit_generator, Report 
                    p(N_X) * fr_mul(fr_mul(k2_3, wxi), chi) + p(N_Y) * fr_mul(fr_mul(k2_3, wyi), zeta);
     const LC aux_x = p(Pi_X) * k2 + p(M_X) * k2_2 + p(N_X) * k2_3;
     const LC aux_y = p(Pi_Y) * k2 + p(M_Y) * k2_2 + p(N_Y) * k2_3;
-    std::vector<pairing::Pair> pairs = {{(lhs + aux).point(pts), q[H]},
-                                        {pts[B], q[Alpha4]},
-                                        {pts[U], q[Alpha]},
-                                        {pts[V], q[Alpha2]},
-                                        {pts[W], q[Alpha3]},
-                                        {(p(O_pub_fix) + p(O_pub_free)).neg().point(pts), q[Gamma]},
-                                        {pairing::g1_neg(pts[O_mid]), q[Eta]},
-                                        {pairing::g1_neg(pts[O_prv]), q[Delta]},
-                                        {aux_x.neg().point(pts), q[X2]},
-                                        {aux_y.neg().point(pts), q[Y2]}};
-    if (!pairing::product_is_one(pairs)) return refuse("pairing product != 1");
+    Combination cmb;
+    cmb.kappa2 = k2;
+    cmb.slot = {lhs + aux, p(B), p(U), p(V), p(W), (p(O_pub_fix) + p(O_pub_free)).neg(), p(O_mid).neg(), p(O_prv).neg(), aux_x.neg(), aux_y.neg()};
+    return cmb;
+}
+// The deciding part: the ten combinations over the proof's checked points, one product of ten pairings against 1
+inline bool decide(const Combination &cmb, const G1Aff *pts, const Sigma2 &s2) {
+    std::vector<pairing::Pair> pairs(kSlots);
+    for (int j = 0; j < kSlots; j++) pairs[j] = {cmb.slot[j].point(pts), s2.q[slot_g2(j)]};
+    return pairing::product_is_one(pairs);
+}
+
+// Verifier::verify_snark.  kappa2 = nullptr: fresh randomness.  Returns rep.ok; throws only for invalid setup parameters / generator.
+inline bool verify_loaded(const Inputs &in, uint32_t explicit_generator, Report &rep, const ScalarField *kappa2_in = nullptr) {
+    rep = Report{};
+    rep.generator = generator_in_effect(explicit_generator);
+    validate_shape(in.sp);
+    if (in.a_pub.size() != in.sp.l_free) throw Error("instance.json: expected l_free public inputs");
+    auto refuse = [&](const std::string &why) {
+        rep.ok = false, rep.reason = why;
+        return false;
+    };
+    Sigma2 s2;
+    check_sigma2(in, s2);
+    if (!s2.reason.empty()) return refuse(s2.reason);
+    G1Aff pts[PtCount];
+    for (int i = 0; i < PtCount; i++) {
+        const char *why = pairing::g1_check(in.pt[i], pts[i]);
+        if (*why) return refuse(g1_reason(in, i, why));
+    }
+    const Combination cmb = combine(in, rep, kappa2_in);
+    if (!decide(cmb, pts, s2)) return refuse("pairing product != 1");
     rep.ok = true;
     return true;
 }
@@ -392,6 +432,289 @@ inline bool verify_files(const std::string &lib_dir, const std::string &crs_dir,
     read_preprocess(preprocess_dir, in);
     read_proof(proof_dir, in);
     return verify_loaded(in, explicit_generator, rep);
+}
+
+// ---- Batch verification: N proofs of one circuit against one reference string, one ten-pair product when all are honest ----
+// Every proof is checked against the same ten G2 points, and every G1 input of its ten pairs is a combination LC_{k,j} of named points.
+// With weights r_k the product over a set S of proofs collapses to  prod_j e(F_j, Q_j) = 1,  F_j = sum_{k in S} r_k LC_{k,j}:  ten pairs
+// again, the ten F_j being ten multi-scalar multiplications (a Folder does them: on the host here, on the device in
+// tkmk_verify_device.hpp).
+// SOUNDNESS.  The product is a polynomial of degree 1 in every r_k over GT (an r-order group), and it is not the constant 1 when some
+// proof of S fails its own equation; r_k is drawn from getrandom() AFTER every input is loaded, uniformly from [1, 2^128), so a set with a
+// false proof passes a fold with probability <= 2^-128 (Schwartz-Zippel over the 128-bit box).  Weights are never derived from a counter
+// or a stream cipher of a short seed, and every fold — the re-folds of a bisection too — draws new ones: two tampered proofs whose
+// errors cancel under EQUAL weights do not cancel under these.  Each proof also keeps its own kappa2, which folds its own equations.
+// MEMBERSHIP IS NEVER FOLDED: E(Fp) has a cofactor, and a random combination does not detect a small-order component (it vanishes in the
+// pairing), so every distinct G1 record is checked — canonical, on the curve, order r — and a proof with a bad record is false with the
+// single verifier's reason and enters no fold.  Records shared by many items (G, sigma_1.x, sigma_1.y, lagrange_KL; s0, s1, O_pub_fix of
+// items with the same preprocess records) are ONE record: checked once, their coefficients added into one term.
+// VERDICTS ARE PER PROOF: if the fold of all surviving items passes, they are all true (one product).  If not, the set is halved and the
+// halves folded again with new weights until the false items stand alone: at most 1 + 2 b ceil(log2 N) products for b false items among
+// N (every failing set of more than one item costs two products, and there are at most b of them on each of the ceil(log2 N) levels).
+struct BatchItem {
+    std::string synthesizer_dir, preprocess_dir, proof_dir;
+};
+struct FoldTerm {
+    ScalarField scalar;
+    uint32_t record;   // index into the batch's table of distinct records
+};
+// "scalars x points per slot" -> ten affine points, and the membership pass over the distinct records
+struct Folder {
+    virtual ~Folder() = default;
+    virtual const char *route() const = 0;
+    // verdict[i] = 0 (fine; the all-zero record is infinity and passes) or ONE of TKMK_G1_BAD_NONCANONICAL / _OFF_CURVE / _NOT_IN_SUBGROUP:
+    // the first check of pairing::g1_check that record i fails
+    virtual void membership(const std::vector<tkmk_g1_affine> &records, std::vector<uint8_t> &verdict) = 0;
+    // out[j] = sum_t slot[j][t].scalar * records[slot[j][t].record]; only records that passed membership are named
+    virtual void fold(const std::vector<tkmk_g1_affine> &records, const std::vector<FoldTerm> (&slot)[kSlots], tkmk_g1_affine (&out)[kSlots]) = 0;
+};
+inline const char *g1_verdict_words(uint8_t v) {   // the words of pairing::g1_check for a verdict byte
+    return v & TKMK_G1_BAD_NONCANONICAL ? "has a coordinate that is not reduced (>= p)" : v & TKMK_G1_BAD_OFF_CURVE ? "is not on the curve" : v ? "is not in the subgroup of order r" : "";
+}
+// fn(i) for i in [0, n) on the process's host threads (TKMK_HOST_THREADS); the first exception is rethrown
+template <class F>
+inline void for_each_index(size_t n, F &&fn) {
+    const unsigned threads = (unsigned)std::min<size_t>(host_threads(), n);
+    std::atomic<size_t> next{0};
+    fastparse::parallel(threads ? threads : 1, [&](unsigned) {
+        for (size_t i = next++; i < n; i = next++) fn(i);
+    });
+}
+struct HostFolder : Folder {   // pairing::g1_mul / g1_add, as LC::point
+    const char *route() const override { return "host"; }
+    void membership(const std::vector<tkmk_g1_affine> &records, std::vector<uint8_t> &verdict) override {
+        verdict.assign(records.size(), 0);
+        for_each_index(records.size(), [&](size_t i) {
+            G1Aff pt;
+            const char *why = pairing::g1_check(records[i], pt);
+            if (*why) verdict[i] = !pairing::g1_decode(records[i], pt) ? TKMK_G1_BAD_NONCANONICAL : !pairing::g1_on_curve(pt) ? TKMK_G1_BAD_OFF_CURVE : TKMK_G1_BAD_NOT_IN_SUBGROUP;
+        });
+    }
+    void fold(const std::vector<tkmk_g1_affine> &records, const std::vector<FoldTerm> (&slot)[kSlots], tkmk_g1_affine (&out)[kSlots]) override {
+        struct Job {
+            int slot;
+            const FoldTerm *t;
+        };
+        std::vector<Job> jobs;
+        for (int j = 0; j < kSlots; j++)
+            for (const FoldTerm &t : slot[j]) jobs.push_back({j, &t});
+        const size_t chunk = 8, n_chunks = (jobs.size() + chunk - 1) / chunk;
+        std::vector<std::array<pairing::G1Jac, kSlots>> part(n_chunks);
+        for_each_index(n_chunks, [&](size_t c) {
+            for (auto &a : part[c]) a = pairing::g1_jac_inf();
+            for (size_t k = c * chunk; k < std::min(jobs.size(), (c + 1) * chunk); k++) {
+                G1Aff pt;
+                if (!pairing::g1_decode(records[jobs[k].t->record], pt)) throw Error("verify_batch: a record that failed membership entered a fold");
+                if (pt.inf || fr_is_zero(jobs[k].t->scalar)) continue;
+                part[c][jobs[k].slot] = pairing::g1_add(part[c][jobs[k].slot], pairing::g1_mul(jobs[k].t->scalar, pt));
+            }
+        });
+        for (int j = 0; j < kSlots; j++) {
+            pairing::G1Jac acc = pairing::g1_jac_inf();
+            for (size_t c = 0; c < n_chunks; c++) acc = pairing::g1_add(acc, part[c][j]);
+            out[j] = pairing::g1_encode(pairing::g1_to_affine(acc));
+        }
+    }
+};
+struct BatchReport {
+    uint32_t generator = 0;
+    bool ok = false;            // every item is true
+    std::string route;
+    uint64_t products = 0;      // pairing products computed
+    std::vector<Report> items;
+    double parse_s = 0, membership_s = 0, fold_s = 0, pairings_s = 0, total_s = 0;
+    std::string to_json() const {
+        auto num = [](double v) {
+            char b[32];
+            snprintf(b, sizeof b, "%.6f", v);
+            return std::string(b);
+        };
+        std::string d = "{\"generator\": " + std::to_string(generator) + ", \"ok\": " + (ok ? "true" : "false") + ", \"n\": " + std::to_string(items.size()) +
+                        ", \"route\": \"" + route + "\", \"products\": " + std::to_string(products) + ", \"items\": [";
+        for (size_t k = 0; k < items.size(); k++) d += (k ? ", " : "") + items[k].to_json();
+        return d + "], \"seconds\": {\"parse\": " + num(parse_s) + ", \"membership\": " + num(membership_s) + ", \"fold\": " + num(fold_s) + ", \"pairings\": " +
+               num(pairings_s) + ", \"total\": " + num(total_s) + "}}";
+    }
+};
+inline ScalarField random_fold_weight() {   // uniform in [1, 2^128), straight from getrandom()
+    for (;;) {
+        frh::U256 v{{0, 0, 0, 0}};
+        if (::getrandom(v.l, 16, 0) != 16) throw Error("getrandom failed: no entropy source for the fold's weights");
+        if (v.l[0] | v.l[1]) return frh::store(v);
+    }
+}
+
+// shared: the setup parameters, G / sigma_1.x / sigma_1.y / lagrange_KL, Sigma2 and the label of the reference string (the item fields of
+// an Inputs are not read).  sigma2_cache (optional): a Sigma2 checked earlier for the SAME reference string (a context keeps one); when
+// null or not yet filled it is checked here, once.  Returns rep.ok; rep.items[k].ok is the verdict of item k and equals what
+// verify_files says for that item alone.  Throws for n == 0, for invalid setup parameters, and for an item whose documents cannot be read
+// or parsed — the message names the item index and the file, and no verdict is given.
+inline bool verify_batch(const Inputs &shared, const std::vector<BatchItem> &items, uint32_t explicit_generator, Folder &folder, BatchReport &rep,
+                         std::unique_ptr<Sigma2> *sigma2_cache = nullptr) {
+    using clk = std::chrono::steady_clock;
+    auto since = [](clk::time_point t) { return std::chrono::duration<double>(clk::now() - t).count(); };
+    const auto t_all = clk::now();
+    const size_t n = items.size();
+    rep = BatchReport{};
+    rep.generator = generator_in_effect(explicit_generator);
+    rep.route = folder.route();
+    if (n == 0) throw Error("verify_batch: an empty batch has no verdict (n must be at least 1)");
+    if (n >= (1u << 24)) throw Error("verify_batch: too many items");
+    validate_shape(shared.sp);
+    root_of_unity(rep.generator, 2);   // a generator that cannot be used is refused before any work
+
+    // ---- per item: parse (all host threads) ----
+    auto t0 = clk::now();
+    std::vector<Inputs> in(n);
+    std::vector<std::string> failed(n);
+    for_each_index(n, [&](size_t k) {
+        try {
+            Inputs &it = in[k];
+            it.sp = shared.sp, it.crs_label = shared.crs_label;
+            for (int i = CRS_G; i < PtCount; i++) it.pt[i] = shared.pt[i];
+            it.a_pub = read_instance(items[k].synthesizer_dir, it.sp);
+            read_preprocess(items[k].preprocess_dir, it);
+            read_proof(items[k].proof_dir, it);
+            if (it.a_pub.size() != it.sp.l_free) throw Error("instance.json: expected l_free public inputs");
+        } catch (const std::exception &e) {
+            failed[k] = std::string(e.what()).empty() ? "unreadable" : e.what();
+        }
+    });
+    for (size_t k = 0; k < n; k++)
+        if (!failed[k].empty())
+            throw Error("verify_batch: item " + std::to_string(k) + ": " + failed[k] + " (synthesizer " + items[k].synthesizer_dir + ", preprocess " + items[k].preprocess_dir +
+                        ", proof " + items[k].proof_dir + ")");
+    rep.items.assign(n, Report{});
+    for (Report &r : rep.items) r.generator = rep.generator;
+    rep.parse_s = since(t0);
+    auto finish = [&] {
+        rep.ok = true;
+        for (const Report &r : rep.items) rep.ok &= r.ok;
+        rep.total_s = since(t_all);
+        return rep.ok;
+    };
+
+    // ---- Sigma2, once ----
+    t0 = clk::now();
+    std::unique_ptr<Sigma2> own;
+    std::unique_ptr<Sigma2> &s2p = sigma2_cache ? *sigma2_cache : own;
+    if (!s2p) {
+        s2p.reset(new Sigma2());
+        check_sigma2(shared, *s2p);
+    }
+    const Sigma2 &s2 = *s2p;
+    if (!s2.reason.empty()) {
+        for (Report &r : rep.items) r.reason = s2.reason;
+        rep.membership_s = since(t0);
+        return finish();
+    }
+
+    // ---- membership: every distinct record once ----
+    std::vector<tkmk_g1_affine> records;
+    std::vector<std::array<uint32_t, PtCount>> rec_of(n);
+    {
+        std::map<std::string, uint32_t> seen;   // the shared records by content: reference string and preprocess
+        for (size_t k = 0; k < n; k++)
+            for (int i = 0; i < PtCount; i++) {
+                if (i < kProofPoints) {
+                    rec_of[k][i] = (uint32_t)records.size();
+                    records.push_back(in[k].pt[i]);
+                    continue;
+                }
+                const std::string key(reinterpret_cast<const char *>(&in[k].pt[i]), sizeof(tkmk_g1_affine));
+                auto at = seen.find(key);
+                if (at == seen.end()) {
+                    at = seen.emplace(key, (uint32_t)records.size()).first;
+                    records.push_back(in[k].pt[i]);
+                }
+                rec_of[k][i] = at->second;
+            }
+    }
+    std::vector<uint8_t> verdict;
+    folder.membership(records, verdict);
+    if (verdict.size() != records.size()) throw Error("verify_batch: the membership pass returned a wrong count");
+    std::vector<size_t> live;
+    for (size_t k = 0; k < n; k++) {
+        int bad = -1;
+        for (int i = 0; i < PtCount && bad < 0; i++)
+            if (verdict[rec_of[k][i]]) bad = i;
+        if (bad < 0) live.push_back(k);
+        else rep.items[k].reason = g1_reason(in[k], bad, g1_verdict_words(verdict[rec_of[k][bad]]));
+    }
+    rep.membership_s = since(t0);
+
+    // ---- per surviving item: transcript, kappa2, a_pub(chi), the ten combinations (all host threads) ----
+    t0 = clk::now();
+    std::vector<Combination> cmb(n);
+    for_each_index(live.size(), [&](size_t a) { cmb[live[a]] = combine(in[live[a]], rep.items[live[a]]); });
+    rep.parse_s += since(t0);
+
+    // ---- folds: new weights every time; the pairing stays on the host ----
+    std::vector<ScalarField> coef[kSlots];
+    auto passes = [&](const size_t *set, size_t count) {
+        auto t1 = clk::now();
+        for (auto &c : coef) c.assign(records.size(), ScalarField{});
+        for (size_t a = 0; a < count; a++) {
+            const size_t k = set[a];
+            const ScalarField r = random_fold_weight();
+            for (int j = 0; j < kSlots; j++)
+                for (int i = 0; i < PtCount; i++) {
+                    const ScalarField &c = cmb[k].slot[j].c[i];
+                    if (!fr_is_zero(c)) coef[j][rec_of[k][i]] = fr_add(coef[j][rec_of[k][i]], fr_mul(r, c));
+                }
+        }
+        static const uint8_t zero[sizeof(tkmk_g1_affine)] = {};
+        std::vector<FoldTerm> slot[kSlots];
+        for (int j = 0; j < kSlots; j++)
+            for (uint32_t i = 0; i < records.size(); i++)
+                if (!fr_is_zero(coef[j][i]) && std::memcmp(&records[i], zero, sizeof zero) != 0) slot[j].push_back({coef[j][i], i});
+        tkmk_g1_affine f[kSlots];
+        folder.fold(records, slot, f);
+        rep.fold_s += since(t1);
+        t1 = clk::now();
+        std::vector<pairing::Pair> pairs(kSlots);
+        for (int j = 0; j < kSlots; j++) {
+            if (!pairing::g1_decode(f[j], pairs[j].p)) throw Error("verify_batch: a folded point is not reduced");
+            pairs[j].q = s2.q[slot_g2(j)];
+        }
+        const bool one = pairing::product_is_one(pairs);
+        rep.products++;
+        rep.pairings_s += since(t1);
+        return one;
+    };
+    // known_false: the set is known to hold a false item (its sibling passed), so its own product is saved
+    std::function<void(const size_t *, size_t, bool)> settle = [&](const size_t *set, size_t count, bool known_false) {
+        if (count == 0) return;
+        if (!known_false && passes(set, count)) {
+            for (size_t a = 0; a < count; a++) rep.items[set[a]].ok = true;
+            return;
+        }
+        if (count == 1) {
+            rep.items[set[0]].reason = "pairing product != 1";
+            return;
+        }
+        const size_t half = (count + 1) / 2;
+        if (passes(set, half)) {
+            for (size_t a = 0; a < half; a++) rep.items[set[a]].ok = true;
+            settle(set + half, count - half, true);
+        } else {
+            settle(set, half, true);
+            settle(set + half, count - half, false);
+        }
+    };
+    settle(live.data(), live.size(), false);
+    return finish();
+}
+
+// the files route: setupParams.json and sigma_verify.json once, then verify_batch
+inline bool verify_batch_files(const std::string &lib_dir, const std::string &crs_dir, const std::vector<BatchItem> &items, uint32_t explicit_generator, Folder &folder,
+                               BatchReport &rep) {
+    if (items.empty()) throw Error("verify_batch: an empty batch has no verdict (n must be at least 1)");
+    Inputs shared;
+    shared.sp = read_shape(lib_dir);
+    validate_shape(shared.sp);
+    read_sigma_verify(crs_dir, shared);
+    return verify_batch(shared, items, explicit_generator, folder, rep);
 }
 
 }  // namespace verify

@@ -20,6 +20,7 @@ TEST_PARTS, COEFFICIENT_BASIS = 1, 2        # TKMK_PROVE_* of include/tkmk_prove
 SYMBOLS = ["tkmk_prover_open", "tkmk_prover_open_sharded", "tkmk_prover_world_size", "tkmk_prover_prove", "tkmk_prover_prove_ex", "tkmk_prover_close", "tkmk_prover_free_string", "tkmk_prover_last_error",
            "tkmk_prover_crs_source", "tkmk_prover_root_generator",
            "tkmk_pairing_product_is_one", "tkmk_verify_files", "tkmk_prover_verify",      # the verifier: bound in tkmk/verify.py
+           "tkmk_verify_batch_files", "tkmk_prover_verify_batch",                        # batch verification: tkmk.verify.verify_batch[_with]
            "tkmk_crs_audit_files", "tkmk_crs_audit_circuit_files"]                                                    # the CRS audit: tkmk.verify.crs_audit
 
 

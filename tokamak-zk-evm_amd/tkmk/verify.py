@@ -1,6 +1,6 @@
 """ctypes binding of the verifier's entries of libtkmk_prover.so (include/tkmk_prover.h; host/tkmk_verify.hpp over host/tkmk_pairing.hpp):
 the work-alike of the reference's `verify` (packages/backend/verify-rust/src/lib.rs: Verifier::init + verify_snark) as library calls.
-Host-only — none of the three touches a device; the same code is the binary tokamak-zk-evm_amd/bin/verify.  Nothing here is Python
+Host-only — none of them touches a device, except the batch entries on route="device", which the caller asks for; the same code is the binary tokamak-zk-evm_amd/bin/verify.  Nothing here is Python
 beyond the call itself."""
 import ctypes
 import json
@@ -19,8 +19,29 @@ def _lib(testing=False):
         l.tkmk_prover_verify.argtypes = [ctypes.c_void_p] + [ctypes.c_char_p] * 3 + [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p)]
         l.tkmk_crs_audit_files.argtypes = [ctypes.c_char_p] * 2 + [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p)]
         l.tkmk_crs_audit_circuit_files.argtypes = l.tkmk_crs_audit_files.argtypes
+        tail = [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p)]
+        l.tkmk_verify_batch_files.argtypes = [ctypes.c_char_p] * 2 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32] + tail
+        l.tkmk_prover_verify_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t] + tail
         l._tkmk_verify_bound = True
     return l
+
+
+ROUTE_HOST, ROUTE_DEVICE = 0, 1            # TKMK_VERIFY_ROUTE_* of include/tkmk_prover.h
+
+
+class VerifyItem(ctypes.Structure):        # tkmk_verify_item
+    _fields_ = [("synthesizer_dir", ctypes.c_char_p), ("preprocess_dir", ctypes.c_char_p), ("proof_dir", ctypes.c_char_p)]
+
+
+def _items(items):
+    arr = (VerifyItem * max(len(items), 1))()
+    for k, (synth, pre, proof) in enumerate(items):
+        arr[k] = VerifyItem(os.fsencode(synth), os.fsencode(pre), os.fsencode(proof))
+    return arr
+
+
+def _route(route):
+    return {"host": ROUTE_HOST, "device": ROUTE_DEVICE}.get(route, route)
 
 
 def _g1_record(p):
@@ -76,6 +97,36 @@ def verify_files(subcircuit_library_dir, crs_dir, synthesizer_dir, preprocess_di
     if code != 0:
         raise service.ProverError(code, "tkmk_verify_files", testing)
     return ok.value == 1, _take_report(l, doc)
+
+
+def verify_batch(subcircuit_library_dir, crs_dir, items, root_generator=0, route="host", testing=False):
+    """tkmk_verify_batch_files: items = [(synthesizer_dir, preprocess_dir, proof_dir)], proofs of ONE circuit against ONE reference string
+    -> (ok_each: list of bool, report).  ok_each[k] is what verify_files says for item k alone; an all-honest batch costs one product of
+    ten pairings (report["products"] == 1), false items are isolated by bisection with fresh weights.  route: "host" (no device call) or
+    "device" (one tkmk_g1_check, one tkmk_msm_multi_ex per fold; TKMK_ERR_NO_DEVICE without one).  report = {"generator", "ok", "n",
+    "route", "products", "items": [a verify_files report per item], "seconds"}.  service.ProverError for an empty batch (code 11) and for
+    unreadable input (the message names the item and the file)."""
+    l = _lib(testing)
+    each, ok, doc = (ctypes.c_uint8 * max(len(items), 1))(), ctypes.c_int(-1), ctypes.c_void_p()
+    code = l.tkmk_verify_batch_files(os.fsencode(subcircuit_library_dir), os.fsencode(crs_dir), ctypes.cast(_items(items), ctypes.c_void_p), len(items),
+                                     int(root_generator), _route(route), ctypes.cast(each, ctypes.c_void_p), ctypes.byref(ok), ctypes.byref(doc))
+    if code != 0:
+        raise service.ProverError(code, "tkmk_verify_batch_files", testing)
+    rep = _take_report(l, doc)
+    return [bool(v) for v in each[:len(items)]], rep
+
+
+def verify_batch_with(prover, items, route="host"):
+    """tkmk_prover_verify_batch: the same against the reference string and generator of an open service.Prover.  route="device" on a
+    sharded context is refused (code 11): its ranks keep the host route"""
+    l = _lib(prover.testing)
+    each, ok, doc = (ctypes.c_uint8 * max(len(items), 1))(), ctypes.c_int(-1), ctypes.c_void_p()
+    code = l.tkmk_prover_verify_batch(prover._h, ctypes.cast(_items(items), ctypes.c_void_p), len(items), _route(route), ctypes.cast(each, ctypes.c_void_p),
+                                      ctypes.byref(ok), ctypes.byref(doc))
+    if code != 0:
+        raise service.ProverError(code, "tkmk_prover_verify_batch", prover.testing)
+    rep = _take_report(l, doc)
+    return [bool(v) for v in each[:len(items)]], rep
 
 
 def crs_audit(subcircuit_library_dir, crs_dir, testing=False, circuit=False):
