@@ -1229,16 +1229,35 @@ static uint32_t msm_resolve_c(uint32_t c_req, uint32_t n_src) {
     return c;
 }
 
-static hipError_t acc_kernels_set_lds(uint32_t bytes) {   // the dynamic-LDS claim is made on every accumulate kernel alike
-    hipError_t e = hipFuncSetAttribute((const void *)k_accumulate_chunks, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+// Dynamic LDS the accumulate kernels claim but never touch: above half a CU's 160 KB a claim holds the kernel to one workgroup (one wave
+// per SIMD) per CU, leaving registers and issue slots to co-resident kernels.
+//   foreground  TKMK_MSM_ACC_LDS=bytes (diagnostic; default none)
+//   background  batches issued on a caller stream marked BACKGROUND (tkmk_stream_set_background: a commit that nothing waits for until
+//               later, issued beside the work that IS waited for) claim 96 KB, so that the foreground's kernels find registers on every
+//               CU while they run.  Measured (r4, one box, alternating): prove4 with its M / N openings in the background 54.4 -> 52.2 ms;
+//               prove0's evaluation commits lose 1 ms the same way (the round ends on them) and stay foreground.
+//               TKMK_MSM_BACKGROUND_LDS overrides the size (0 = off).
+// The kernels' dynamic-LDS limit is raised here, once, to the larger of the two; if the runtime refuses it, neither claim is made.
+struct msm_acc_lds_t {
+    uint32_t foreground, background;
+};
+static const msm_acc_lds_t &msm_acc_lds() {
+    static const msm_acc_lds_t claims = [] {
+        const char *fg = getenv("TKMK_MSM_ACC_LDS"), *bg = getenv("TKMK_MSM_BACKGROUND_LDS");
+        msm_acc_lds_t v{fg ? (uint32_t)atoi(fg) : 0u, bg ? (uint32_t)atoi(bg) : 98304u};
+        const int most = (int)(v.foreground > v.background ? v.foreground : v.background);
+        hipError_t e = most ? hipFuncSetAttribute((const void *)k_accumulate_chunks, hipFuncAttributeMaxDynamicSharedMemorySize, most) : hipSuccess;
 #ifdef TK_MSM_SYM_PRECOMPUTE_ACC
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_accumulate_chunks_rows, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (most && e == hipSuccess) e = hipFuncSetAttribute((const void *)k_accumulate_chunks_rows, hipFuncAttributeMaxDynamicSharedMemorySize, most);
 #endif
-    return e;
+        if (e != hipSuccess) v = msm_acc_lds_t{0, 0};
+        return v;
+    }();
+    return claims;
 }
-static thread_local bool tl_background_batch = false;   // set by msm_pipeline for the jobs it enqueues
+// background: the batch was issued on a caller stream marked BACKGROUND (msm_pipeline asks; a single MSM never is)
 static tkmk_error msm_enqueue(const fr_t *scalars, const g1_affine_t *bases_mont, uint32_t n_src, uint32_t factor, uint32_t c_req,
-                              uint32_t bits, bool scalars_mont, hipStream_t s, g1_xyzz_t *wins_host, msm_plan_t *plan_out,
+                              uint32_t bits, bool scalars_mont, hipStream_t s, g1_xyzz_t *wins_host, msm_plan_t *plan_out, bool background,
                               msm_view_t sv = view_identity(), msm_view_t bv = view_identity(), uint32_t level_rows = 0,
                               const acc_row_t *acc_rows = nullptr) {   // acc_rows: the table as accumulate-ready rows (bases_mont unused)
     msm_plan_t pl;
@@ -1393,26 +1412,8 @@ static tkmk_error msm_enqueue(const fr_t *scalars, const g1_affine_t *bases_mont
     TK_HIP(hipMemsetAsync(d_buckets.p, 0, (size_t)pl.W * pl.B * sizeof(g1_xyzz_t), s));  // empty bucket = infinity
     TK_HIP(hipMemsetAsync(d_big.p, 0, 4, s));
     TK_HIP(hipMemsetAsync(d_giant.p, 0, 4, s));
-    // TKMK_MSM_ACC_LDS=bytes (diagnostic): dynamic LDS the accumulate kernel claims but never touches; above half a CU's 160 KB it
-    // holds the kernel to one workgroup (one wave per SIMD) per CU, leaving registers and issue slots to co-resident kernels
-    static const uint32_t acc_lds = [] {
-        const char *e = getenv("TKMK_MSM_ACC_LDS");
-        uint32_t v = e ? (uint32_t)atoi(e) : 0u;
-        if (v && acc_kernels_set_lds(v) != hipSuccess) v = 0;
-        return v;
-    }();
-    // Batches issued on a caller stream marked BACKGROUND (tkmk_stream_set_background: a commit that nothing waits for until later, issued
-    // beside the work that IS waited for) make the same claim — 96 KB, more than half a CU's LDS — so that their accumulate kernels hold
-    // one workgroup per CU and the foreground's kernels find registers on every CU while they run.  Measured (r4, one box, alternating):
-    // prove4 with its M / N openings in the background 54.4 -> 52.2 ms; prove0's evaluation commits lose 1 ms the same way (the round ends
-    // on them) and stay foreground.  TKMK_MSM_BACKGROUND_LDS overrides the size (0 = off).
-    static const uint32_t bg_lds = [] {
-        const char *e = getenv("TKMK_MSM_BACKGROUND_LDS");
-        uint32_t v = e ? (uint32_t)atoi(e) : 98304u;
-        if (v && acc_kernels_set_lds(v) != hipSuccess) v = 0;
-        return v;
-    }();
-    const uint32_t lds_claim = (tl_background_batch && bg_lds) ? bg_lds : acc_lds;
+    const msm_acc_lds_t &acc_lds = msm_acc_lds();
+    const uint32_t lds_claim = (background && acc_lds.background) ? acc_lds.background : acc_lds.foreground;
     prof.mark("msm.prepare");   // bucket / queue memsets, the entry counter: keeps "msm.accumulate" to the kernel itself
 #ifdef TK_MSM_SYM_PRECOMPUTE_ACC
     if (acc_rows)
@@ -1488,7 +1489,7 @@ static tkmk_error msm_one(const fr_t *scalars, const g1_affine_t *bases_mont, ui
     std::vector<g1_xyzz_t> wins_v((size_t)MSM_MAX_WINDOWS * MSM_WIN_PARTS);
     g1_xyzz_t *wins = wins_v.data();
     msm_plan_t pl;
-    TK_TRY(msm_enqueue(scalars, bases_mont, n, factor, c_req, bits, scalars_mont, s, wins, &pl));
+    TK_TRY(msm_enqueue(scalars, bases_mont, n, factor, c_req, bits, scalars_mont, s, wins, &pl, false));
     TK_HIP(hipStreamSynchronize(s));
     *result_host = msm_horner(pl, wins);
     return TKMK_SUCCESS;
@@ -1584,7 +1585,7 @@ static tkmk_error msm_pipeline(const std::vector<msm_pipe_job> &jobs, uint32_t c
                                hipStream_t caller, g1_xyzz_t *results) {
     msm_pipe_set &set = msm_pipe_set_of(caller);
     std::lock_guard<std::mutex> lk(set.mu);
-    tl_background_batch = tk_stream_is_background(caller);
+    const bool background = tk_stream_is_background(caller);
     std::vector<msm_slot> &g_slots = set.slots;
     const uint32_t n_streams = tk_msm_pipeline_streams();   // 3 unless TKMK_MSM_STREAMS / tkmk_msm_set_pipeline_streams say otherwise
     const uint32_t K = jobs.size() < n_streams ? (uint32_t)jobs.size() : n_streams;
@@ -1614,7 +1615,7 @@ static tkmk_error msm_pipeline(const std::vector<msm_pipe_job> &jobs, uint32_t c
                                jb.bases_mont ? 1 : 0, jb.bv);   // the converted copy is gathered: point k at row k
             bm = d_bm.as<g1_affine_t>();
         }
-        err = msm_enqueue(jb.scalars, bm, jb.n, jb.factor, jb.c ? jb.c : c_req, bits, scalars_mont, sl.s, sl.wins, &sl.pl, jb.sv,
+        err = msm_enqueue(jb.scalars, bm, jb.n, jb.factor, jb.c ? jb.c : c_req, bits, scalars_mont, sl.s, sl.wins, &sl.pl, background, jb.sv,
                           jb.convert ? view_identity() : jb.bv, jb.convert ? 0u : jb.level_rows,
                           jb.acc_rows && !jb.convert ? (const acc_row_t *)jb.bases : nullptr);
         if (err != TKMK_SUCCESS) break;

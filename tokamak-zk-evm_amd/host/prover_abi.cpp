@@ -3,8 +3,6 @@
 // and, with -DTKMK_TESTING_MODE, libtkmk_prover_testing.so for the differential tests (the reference's `testing-mode` feature).
 // Both carry the verifier's entries (host/tkmk_verify.hpp, host/tkmk_pairing.hpp): pure host work, no device call — except the device route
 // of the two batch entries (host/tkmk_verify_device.hpp), which the caller asks for.
-#include <dlfcn.h>
-
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
@@ -83,51 +81,12 @@ static char *dup_string(const std::string &doc) {
     return s;
 }
 
-// the entries of libtkmk_dist.so a sharded context calls, resolved at run time: the prover library itself does not link RCCL, and the
-// host that made the communicator has the library in the process already
-static ShardLink link_for(void *comm) {
-    void *h = dlopen("libtkmk_dist.so", RTLD_NOW | RTLD_NOLOAD);
-    if (!h) {   // not loaded under that name: next to this library
-        Dl_info info;
-        if (dladdr((void *)&link_for, &info) && info.dli_fname) {
-            std::string dir = info.dli_fname;
-            size_t s = dir.rfind('/');
-            dir = s == std::string::npos ? "." : dir.substr(0, s);
-            h = dlopen((dir + "/libtkmk_dist.so").c_str(), RTLD_NOW);
-        }
-    }
-    if (!h) throw Error("tkmk_prover_open_sharded: libtkmk_dist.so is not loaded and was not found next to libtkmk_prover.so");
-    ShardLink l;
-    l.comm = comm;
-    auto sym = [&](const char *name) {
-        void *p = dlsym(h, name);
-        if (!p) throw Error(std::string("tkmk_prover_open_sharded: libtkmk_dist.so lacks ") + name);
-        return p;
-    };
-    l.multi_ex_sharded = (decltype(l.multi_ex_sharded))sym("tkmk_msm_multi_ex_sharded");
-    l.broadcast_host = (decltype(l.broadcast_host))sym("tkmk_comm_broadcast_host");
-    l.device_turn = (decltype(l.device_turn))sym("tkmk_comm_device_turn");
-    l.all_gather_host = (decltype(l.all_gather_host))sym("tkmk_comm_all_gather_host");
-    l.agree = (decltype(l.agree))sym("tkmk_comm_agree");
-    l.abort = (decltype(l.abort))sym("tkmk_comm_abort");
-    l.fwd_cols_to_rows = (decltype(l.fwd_cols_to_rows))sym("tkmk_dist_fwd_cols_to_rows");
-    l.inv_rows_to_cols = (decltype(l.inv_rows_to_cols))sym("tkmk_dist_inv_rows_to_cols");
-    l.rows_rotate = (decltype(l.rows_rotate))sym("tkmk_dist_rows_rotate");
-    l.ring_shift = (decltype(l.ring_shift))sym("tkmk_comm_ring_shift");
-    l.relayout_cols_to_rows = (decltype(l.relayout_cols_to_rows))sym("tkmk_dist_relayout_cols_to_rows");
-    l.relayout_rows_to_cols = (decltype(l.relayout_rows_to_cols))sym("tkmk_dist_relayout_rows_to_cols");
-    int world = ((int (*)(const void *))sym("tkmk_comm_size"))(comm), rank = ((int (*)(const void *))sym("tkmk_comm_rank"))(comm);
-    if (world < 1 || rank < 0 || rank >= world) throw Error("tkmk_prover_open_sharded: invalid communicator");
-    l.shard = Shard{(uint32_t)world, (uint32_t)rank};
-    return l;
-}
-
 TKP_API tkmk_error tkmk_prover_open_sharded(void *comm, const char *subcircuit_library_dir, const char *crs_dir, tkmk_prover **out) {
     if (!comm || !subcircuit_library_dir || !crs_dir || !out) return TKMK_ERR_INVALID_POINTER;
     return guarded([&] {
         int ndev = 0;
         if (tkmk_device_count(&ndev) != TKMK_SUCCESS || ndev < 1) throw Error(TKMK_ERR_NO_DEVICE, "tkmk_prover_open_sharded: no HIP device (the MI355X backend has no CPU fallback)");
-        ShardLink link = link_for(comm);
+        ShardLink link = ShardLink::resolve(comm);   // the entries of libtkmk_dist.so, resolved at run time
         std::string crs = crs_dir;
         std::unique_ptr<tkmk_prover> p(new tkmk_prover());
         p->ctx = ProverContext::open(

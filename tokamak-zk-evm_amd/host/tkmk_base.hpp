@@ -63,4 +63,20 @@ inline bool fr_is_zero(const ScalarField &a) {
 }
 inline bool fr_eq(const ScalarField &a, const ScalarField &b) { return std::memcmp(&a, &b, sizeof a) == 0; }
 
+// an MSM result -> affine: canonical (x, y, 1), so dropping z is G1Affine::from(projective); (0, 1, 0) -> (0, 0) = G1serde::zero()
+inline G1Affine projective_to_affine(const tkmk_g1_projective &r) {
+    G1Affine out{};
+    bool inf = true;
+    for (uint32_t l : r.z.limbs) inf &= l == 0;
+    if (!inf) out.x = r.x, out.y = r.y;
+    return out;
+}
+// TKMK_FR_ROOT_GENERATOR=<g> pins the root-of-unity generator (include/tkmk.h; the rule of the device library, csrc/ntt.hip):
+// the value, or 0 when the variable is unset or outside [2, 65536)
+inline uint32_t pinned_root_generator() {
+    const char *e = std::getenv("TKMK_FR_ROOT_GENERATOR");
+    const int v = e ? std::atoi(e) : 0;
+    return v >= 2 && v < 65536 ? (uint32_t)v : 0u;
+}
+
 }  // namespace tkmk

@@ -11,6 +11,11 @@
 // Every method is a few calls into libtkmk_hip.so; the coefficient matrix stays in HBM (the reference copies it to the
 // host for find_degree / resize / mul_monomial / scaling / divisions).  Header-only; link with -ltkmk_hip.
 #pragma once
+#include <dlfcn.h>
+
+#include <future>
+
+#include "../../include/tkmk_dist.h"
 #include "tkmk_base.hpp"
 #include "tkmk_fr.hpp"
 
@@ -91,6 +96,11 @@ inline tkmk_vecops_config dev_cfg() {
     c.is_a_on_device = c.is_b_on_device = c.is_result_on_device = true;
     return c;
 }
+inline tkmk_msm_config msm_dev_cfg() {   // scalars and points in HBM, results to the host
+    tkmk_msm_config cfg = tkmk_msm_default_config();
+    cfg.are_scalars_on_device = cfg.are_points_on_device = true;
+    return cfg;
+}
 
 // ---- One proof over G GPUs: the calling thread's place in a sharded prover (no reference counterpart) ----
 // world == 1 (the default): everything below is the single-GPU code path, unchanged.  world > 1 (installed for the span of a call by
@@ -104,14 +114,67 @@ struct Shard {
     size_t cols_of(size_t total) const { return total > rank ? (total - rank + world - 1) / world : 0; }   // |{iy < total : iy = rank mod world}|
     size_t rows_of(size_t total) const { return cols_of(total); }                                         // the same count for an interleaved row set
 };
-struct DistCtx {
-    void *comm = nullptr;
+// The communicator of a sharded prover and the entries of libtkmk_dist.so it is used through: THE one table of them on the host side
+// (signatures from include/tkmk_dist.h).  They arrive as pointers resolved at run time — what is built from these headers does not link
+// RCCL, and the host that made the communicator has the library in the process already.
+struct ShardLink {
+    tkmk_comm *comm = nullptr;
     Shard shard;
-    tkmk_error (*all_gather_host)(void *, const void *, size_t, void *) = nullptr;
-    tkmk_error (*fwd_cols_to_rows)(void *, const tkmk_fr *, size_t, size_t, size_t, size_t, int, tkmk_fr *) = nullptr;
-    tkmk_error (*inv_rows_to_cols)(void *, tkmk_fr *, size_t, size_t, int, tkmk_fr *) = nullptr;
-    tkmk_error (*rows_rotate)(void *, const tkmk_fr *, size_t, size_t, size_t, tkmk_fr *) = nullptr;
-    tkmk_error (*ring_shift)(void *, const void *, size_t, int, void *) = nullptr;
+    decltype(&tkmk_msm_multi_ex_sharded) multi_ex_sharded = nullptr;
+    decltype(&tkmk_comm_broadcast_host) broadcast_host = nullptr;
+    decltype(&tkmk_comm_device_turn) device_turn = nullptr;
+    decltype(&tkmk_comm_all_gather_host) all_gather_host = nullptr;
+    decltype(&tkmk_comm_agree) agree = nullptr;
+    decltype(&tkmk_comm_abort) abort = nullptr;
+    decltype(&tkmk_dist_fwd_cols_to_rows) fwd_cols_to_rows = nullptr;
+    decltype(&tkmk_dist_inv_rows_to_cols) inv_rows_to_cols = nullptr;
+    decltype(&tkmk_dist_rows_rotate) rows_rotate = nullptr;
+    decltype(&tkmk_comm_ring_shift) ring_shift = nullptr;
+    decltype(&tkmk_dist_relayout_cols_to_rows) relayout_cols_to_rows = nullptr;
+    decltype(&tkmk_dist_relayout_rows_to_cols) relayout_rows_to_cols = nullptr;
+    explicit operator bool() const { return comm != nullptr; }
+    // the table for `comm`, from the libtkmk_dist.so of this process: the one already loaded under that name, else the one next to the
+    // object this code was built into (link with -ldl)
+    static ShardLink resolve(void *comm) {
+        void *h = dlopen("libtkmk_dist.so", RTLD_NOW | RTLD_NOLOAD);
+        Dl_info info;
+        if (!h && dladdr((void *)&ShardLink::resolve, &info) && info.dli_fname) {
+            std::string dir = info.dli_fname;
+            const size_t s = dir.rfind('/');
+            dir = s == std::string::npos ? "." : dir.substr(0, s);
+            h = dlopen((dir + "/libtkmk_dist.so").c_str(), RTLD_NOW);
+        }
+        if (!h) throw Error("sharded prover: libtkmk_dist.so is not loaded and was not found next to the prover library");
+        ShardLink l;
+        l.comm = static_cast<tkmk_comm *>(comm);
+        auto sym = [&](auto &fn, const char *name) {
+            void *p = dlsym(h, name);
+            if (!p) throw Error(std::string("sharded prover: libtkmk_dist.so lacks ") + name);
+            fn = reinterpret_cast<std::decay_t<decltype(fn)>>(p);
+        };
+        sym(l.multi_ex_sharded, "tkmk_msm_multi_ex_sharded"), sym(l.broadcast_host, "tkmk_comm_broadcast_host");
+        sym(l.device_turn, "tkmk_comm_device_turn"), sym(l.all_gather_host, "tkmk_comm_all_gather_host");
+        sym(l.agree, "tkmk_comm_agree"), sym(l.abort, "tkmk_comm_abort");
+        sym(l.fwd_cols_to_rows, "tkmk_dist_fwd_cols_to_rows"), sym(l.inv_rows_to_cols, "tkmk_dist_inv_rows_to_cols");
+        sym(l.rows_rotate, "tkmk_dist_rows_rotate"), sym(l.ring_shift, "tkmk_comm_ring_shift");
+        sym(l.relayout_cols_to_rows, "tkmk_dist_relayout_cols_to_rows"), sym(l.relayout_rows_to_cols, "tkmk_dist_relayout_rows_to_cols");
+        decltype(&tkmk_comm_size) size_of = nullptr, rank_of = nullptr;
+        sym(size_of, "tkmk_comm_size"), sym(rank_of, "tkmk_comm_rank");
+        const int world = size_of(l.comm), rank = rank_of(l.comm);
+        if (world < 1 || rank < 0 || rank >= world) throw Error("sharded prover: invalid communicator");
+        l.shard = Shard{(uint32_t)world, (uint32_t)rank};
+        return l;
+    }
+};
+// What the calling thread works under: nothing (one GPU, the default), or a communicator for the span of a call (ShardSpan).  Two
+// questions are asked of it, and a one-rank communicator answers them differently:
+//   installed()  there is a communicator: commit batches go through it (tkmk_msm_multi_ex_sharded, whatever the world size), and nothing
+//                is issued from helper threads beside it
+//   on()         world > 1: matrices are distributed and the methods below use collectives
+struct DistCtx {
+    const ShardLink *link = nullptr;
+    Shard shard;
+    bool installed() const { return link != nullptr; }
     bool on() const { return shard.world > 1; }
     uint32_t G() const { return shard.world; }
     uint32_t r() const { return shard.rank; }
@@ -119,7 +182,7 @@ struct DistCtx {
     template <class T>
     std::vector<T> gather(const T &mine) const {
         std::vector<T> all(shard.world);
-        check(all_gather_host(comm, &mine, sizeof(T), all.data()), "tkmk_comm_all_gather_host");
+        check(link->all_gather_host(link->comm, &mine, sizeof(T), all.data()), "tkmk_comm_all_gather_host");
         return all;
     }
 };
@@ -127,6 +190,22 @@ inline DistCtx &dist_ctx() {
     static thread_local DistCtx c;
     return c;
 }
+// for the span of one call on a sharded context: this thread works under the link's communicator (dist_ctx()), and (loopback transport
+// only) this virtual rank holds the device turn except while it waits for its peers.  An unset link installs nothing.
+struct ShardSpan {
+    const ShardLink &link;
+    explicit ShardSpan(const ShardLink &l) : link(l) {
+        if (!link) return;
+        check(link.device_turn(link.comm, 1), "tkmk_comm_device_turn");
+        dist_ctx() = DistCtx{&link, link.shard};
+    }
+    ShardSpan(const ShardSpan &) = delete;
+    ~ShardSpan() {
+        if (!link) return;
+        dist_ctx() = DistCtx{};
+        (void)link.device_turn(link.comm, 0);
+    }
+};
 
 class DensePolynomialExt {
   public:
@@ -137,7 +216,6 @@ class DensePolynomialExt {
     int64_t x_degree = -1, y_degree = -1;
     size_t x_size = 1, y_size = 1;
     bool rep = true;
-    DeviceVec<ScalarField> commit_slice_;   // sharded prover: this rank's columns of a REPLICATED polynomial while its commit is in flight (Sigma1::job)
 
     DensePolynomialExt() = default;
     DensePolynomialExt(DeviceVec<ScalarField> &&c, size_t xs, size_t ys, int64_t xd, int64_t yd, bool replicated = !dist_ctx().on())
@@ -193,7 +271,7 @@ class DensePolynomialExt {
         if (!dc.on()) return from_rou_evals(evals, x_size, y_size);
         DeviceVec<ScalarField> coeffs(x_size * (y_size / dc.G()));
         host_trace("from_rou_evals %zu x %zu (rank %u of %u)", x_size, y_size, dc.r(), dc.G());
-        check(dc.inv_rows_to_cols(dc.comm, evals.ptr(), x_size, y_size, 0, coeffs.ptr()), "tkmk_dist_inv_rows_to_cols");
+        check(dc.link->inv_rows_to_cols(dc.link->comm, evals.ptr(), x_size, y_size, 0, coeffs.ptr()), "tkmk_dist_inv_rows_to_cols");
         return from_coeffs(std::move(coeffs), x_size, y_size, false);
     }
     // evaluations in the COLS layout — what the witness side produces (one column per placement: u, v, w, b, s0, s1) and prove1's walk
@@ -204,7 +282,7 @@ class DensePolynomialExt {
         if (x_size % dc.G() || y_size % dc.G()) throw Error("from_rou_evals: the domain is smaller than the number of ranks");
         if (evals_cols.len() < x_size * (y_size / dc.G())) throw Error("Insufficient buffer length for from_rou_evals");
         DeviceVec<ScalarField> slab(x_size / dc.G() * y_size);
-        check(dc.fwd_cols_to_rows(dc.comm, evals_cols.ptr(), x_size, y_size, x_size, y_size, 3, slab.ptr()), "tkmk_dist_fwd_cols_to_rows");
+        check(dc.link->fwd_cols_to_rows(dc.link->comm, evals_cols.ptr(), x_size, y_size, x_size, y_size, 3, slab.ptr()), "tkmk_dist_fwd_cols_to_rows");
         return from_rou_evals_consume(std::move(slab), x_size, y_size);
     }
     // small evaluation vectors made from host values (unit evaluations, the public inputs): the same on every rank -> replicated result
@@ -252,7 +330,7 @@ class DensePolynomialExt {
             }
             DeviceVec<ScalarField> out(xs / dc.G() * ys);
             host_trace("evals_on %zu x %zu -> %zu x %zu (rank %u of %u)", x_size, y_size, xs, ys, dc.r(), dc.G());
-            check(dc.fwd_cols_to_rows(dc.comm, poly.ptr(), x_size, y_size, xs, ys, 0, out.ptr()), "tkmk_dist_fwd_cols_to_rows");
+            check(dc.link->fwd_cols_to_rows(dc.link->comm, poly.ptr(), x_size, y_size, xs, ys, 0, out.ptr()), "tkmk_dist_fwd_cols_to_rows");
             return out;
         }
         if (x_size <= xs && y_size <= ys) {
@@ -539,7 +617,7 @@ class DensePolynomialExt {
                 if (std::get<0>(f) == &p && std::get<1>(f) == sft) shifted = std::get<2>(f);
             if (!shifted) {
                 temps.emplace_back(p.x_size * lc);
-                check(dc.ring_shift(dc.comm, p.poly.ptr(), p.x_size * lc * sizeof(ScalarField), (int)sft, temps.back().ptr()), "tkmk_comm_ring_shift");
+                check(dc.link->ring_shift(dc.link->comm, p.poly.ptr(), p.x_size * lc * sizeof(ScalarField), (int)sft, temps.back().ptr()), "tkmk_comm_ring_shift");
                 shifted = temps.back().ptr();
                 fetched.emplace_back(&p, sft, shifted);
             }
@@ -644,7 +722,7 @@ class DensePolynomialExt {
         check(tkmk_poly_div_by_ruffini(poly.ptr(), (uint32_t)x_size, (uint32_t)lc, &x, &y, qx.ptr(), scratch_qy.ptr(), &ignored, nullptr), "div_by_ruffini");
         check(tkmk_poly_eval_x(poly.ptr(), (uint32_t)x_size, (uint32_t)lc, &x, rem.ptr(), nullptr), "div_by_ruffini: remainder row");
         std::vector<ScalarField> mine = rem.to_host(), all(y_size), whole(y_size);
-        check(dc.all_gather_host(dc.comm, mine.data(), lc * sizeof(ScalarField), all.data()), "tkmk_comm_all_gather_host");
+        check(dc.link->all_gather_host(dc.link->comm, mine.data(), lc * sizeof(ScalarField), all.data()), "tkmk_comm_all_gather_host");
         for (size_t q = 0; q < G; q++)
             for (size_t k = 0; k < lc; k++) whole[q + G * k] = all[q * lc + k];
         DeviceVec<ScalarField> row = DeviceVec<ScalarField>::from_host(whole), qrow(y_size), qy(y_size);
@@ -796,7 +874,7 @@ class PolyExpr {
                 if (rot_x % target_x_size) {
                     if (rot_x > h) throw Error("Fused polynomial expression: the root shift spans more than one rank's rows");
                     auto rt = std::make_shared<DeviceVec<ScalarField>>(h * target_y_size);
-                    check(dc.rows_rotate(dc.comm, slab->ptr(), h, target_y_size, rot_x, rt->ptr()), "tkmk_dist_rows_rotate");
+                    check(dc.link->rows_rotate(dc.link->comm, slab->ptr(), h, target_y_size, rot_x, rt->ptr()), "tkmk_dist_rows_rotate");
                     rotated.push_back(rt);
                     slab = rt;
                 }
@@ -996,17 +1074,95 @@ inline std::vector<CommitBox> *&commit_box_sink() {
 // One proof over G GPUs: the commit table xy_powers is sharded like the coefficient matrices it is
 // multiplied with — rank r of G holds the grid columns iy = r mod G (COLS layout, struct Shard above) — so that any coefficient box
 // [0, tx) x [0, ty) splits evenly whatever its width, and a rank's share of a commit is a view of its own columns on both sides.
-// The commit batches of a sharded prover go through its communicator (tkmk_msm_multi_ex_sharded of libtkmk_dist.so: every rank runs
-// its share, ONE all-gather of 144 bytes per commit, the partials summed on the device).  Installed per host thread by the sharded
-// context for the span of a call; absent, batches run on this GPU alone.
-struct CommitComm {
-    void *comm = nullptr;
-    tkmk_error (*multi_ex_sharded)(void *comm, const tkmk_msm_job_ex *jobs, int n_jobs, const tkmk_msm_config *cfg, int bases_form, tkmk_g1_projective *results) = nullptr;
+// The commit batches of a thread that works under a communicator (dist_ctx().installed()) go through it (tkmk_msm_multi_ex_sharded of
+// libtkmk_dist.so: every rank runs its share, ONE all-gather of 144 bytes per commit, the partials summed on the device); otherwise they
+// run on this GPU alone.
+
+// One batch of commitments — the independent MSMs of a round, one pipelined call: the jobs, and every device buffer a job points into
+// that the batch itself made or was given.
+//   OWNED     a sharded rank's columns of a replicated polynomial, cut out when the job is added (Sigma1::job), and the operand lists
+//             handed over with add_indexed: they live exactly as long as the batch, wherever it goes.
+//   BORROWED  matrices a job only views — a polynomial's own `poly`, an evaluation vector, the commit tables.  They must outlive the
+//             batch and the Pending handle made from it: declare the batch or handle AFTER them.
+// Jobs are added on the thread that owns the round (the commit boxes are recorded then, in that thread's sink); the batch then runs there
+// (run) or is handed to a helper thread (start).  Move-only.
+class CommitBatch {
+    std::vector<tkmk_msm_job_ex> jobs_;
+    std::vector<DeviceVec<ScalarField>> scalars_;
+    std::vector<DeviceVec<uint32_t>> indices_;
+
+  public:
+    CommitBatch() = default;
+    CommitBatch(CommitBatch &&) = default;
+    CommitBatch &operator=(CommitBatch &&) = default;
+    void add(const tkmk_msm_job_ex &j) { jobs_.push_back(j); }   // a job over operands the batch owns already, or borrows
+    const ScalarField *keep(DeviceVec<ScalarField> &&v) {         // -> where the buffer, now the batch's, lies
+        scalars_.push_back(std::move(v));
+        return scalars_.back().ptr();
+    }
+    // sum over k < cnt of sc[k] * table[ix[k]] (the binding commitments): the two lists become the batch's, the table is borrowed
+    void add_indexed(DeviceVec<ScalarField> &&sc, DeviceVec<uint32_t> &&ix, uint64_t cnt, const DeviceVec<G1Affine> &table) {
+        indices_.push_back(std::move(ix));
+        tkmk_msm_job_ex j{};
+        j.scalars = keep(std::move(sc)), j.bases = table.ptr(), j.msm_size = (int)cnt, j.base_index = indices_.back().ptr(), j.base_table_len = table.len();
+        add(j);
+    }
+    // the jobs in one pipelined call over converted tables -> affine results; (0,0) = G1serde::zero()
+    // stream: the caller's stream for the batch's scratch frame (a helper thread names its own, so that its frame does not share the
+    // default stream's arena with the main thread: tkmk.h "re-entrant per stream")
+    // under: what the batch's jobs were made under — the calling thread's context, or the one a helper was handed by its starter
+    std::vector<G1Affine> run(tkmk_stream stream = nullptr, const DistCtx &under = dist_ctx()) const {
+        tkmk_msm_config cfg = msm_dev_cfg();
+        cfg.stream_handle = stream;
+        std::vector<tkmk_g1_projective> res(jobs_.size());
+        if (host_trace_on()) {
+            std::string d;
+            for (auto &j : jobs_) d += " " + std::to_string(j.msm_size) + (j.table_c ? "t" : "") + (j.base_index ? "i" : "");
+            host_trace("commit batch of %zu:%s", jobs_.size(), d.c_str());
+        }
+        if (under.installed())
+            check(under.link->multi_ex_sharded(under.link->comm, jobs_.data(), (int)jobs_.size(), &cfg, TKMK_BASES_ACC_READY, res.data()), "tkmk_msm_multi_ex_sharded");
+        else check(tkmk_msm_multi_ex(jobs_.data(), (int)jobs_.size(), &cfg, TKMK_BASES_ACC_READY, res.data()), "tkmk_msm_multi_ex");
+        std::vector<G1Affine> out;
+        for (auto &r : res) out.push_back(projective_to_affine(r));
+        return out;
+    }
+    // A batch running on a helper thread: owns the batch and the future.  The destructor waits, so what the batch borrows is safe
+    // as long as it was declared before the handle; get() collects the results (and rethrows what the helper met).
+    class Pending {
+        std::unique_ptr<const CommitBatch> batch_;
+        std::future<std::vector<G1Affine>> result_;
+        friend class CommitBatch;
+
+      public:
+        Pending() = default;
+        Pending(Pending &&) = default;
+        Pending &operator=(Pending &&o) {
+            wait();
+            batch_ = std::move(o.batch_), result_ = std::move(o.result_);
+            return *this;
+        }
+        ~Pending() { wait(); }
+        bool valid() const { return result_.valid(); }
+        void wait() const {
+            if (result_.valid()) result_.wait();
+        }
+        std::vector<G1Affine> get() { return result_.get(); }
+    };
+    // hands the batch to a helper thread, which runs `first` (if any) and then the batch on `stream`, under the starter's context.
+    // What the jobs read must be complete by now: a stream of tkmk_stream_create does not order itself behind the default stream.
+    Pending start(tkmk_stream stream, std::function<void()> first = nullptr) && {
+        Pending p;
+        p.batch_.reset(new CommitBatch(std::move(*this)));
+        const CommitBatch *b = p.batch_.get();
+        const DistCtx under = dist_ctx();
+        p.result_ = std::async(std::launch::async, [b, stream, under, first] {
+            if (first) first();
+            return b->run(stream, under);
+        });
+        return p;
+    }
 };
-inline CommitComm &commit_comm() {
-    static thread_local CommitComm c;
-    return c;
-}
 
 // one row of a commit table in the accumulate-ready form (include/tkmk.h: TKMK_BASES_ACC_READY; opaque here)
 struct alignas(128) AccRow {
@@ -1081,13 +1237,13 @@ class Sigma1 {
         return out;
     }
     uint32_t table_c() const { return table_c_; }
-    // a table job: the same rows, addressed in the accumulate-ready table (run_jobs passes TKMK_BASES_ACC_READY, decided per job)
+    // a table job: the same rows, addressed in the accumulate-ready table (CommitBatch::run passes TKMK_BASES_ACC_READY, decided per job)
     void use_table(tkmk_msm_job_ex &j) const {
         j.bases = reinterpret_cast<const G1Affine *>(table_.ptr());
         j.table_c = table_c_, j.table_factor = table_factor_;
     }
-    // the MSM job of one commit: coefficient box x CRS sub-grid, both as views (msm_size 0 for the zero polynomial)
-    tkmk_msm_job_ex job(DensePolynomialExt &poly, const char *name = nullptr) const {
+    // adds the MSM job of one commit: coefficient box x CRS sub-grid, both as views (msm_size 0 for the zero polynomial)
+    void job(CommitBatch &batch, const DensePolynomialExt &poly, const char *name = nullptr) const {
         // the box the MSM runs over: the polynomial's degree bound (DensePolynomialExt::shape_degree) — or its MEASURED degree when the
         // caller records the boxes (the reference's own encode_poly measures: iotools/mod.rs:2055-2060; tests/golden/encode_dims.json).
         // A view addresses the box inside the matrix as it is: nothing is resized or copied.
@@ -1097,16 +1253,15 @@ class Sigma1 {
         if (tx > rs_x_ || ty > rs_y_) throw Error("Insufficient length of sigma.sigma_1.xy_powers");
         if (auto *sink = commit_box_sink()) sink->push_back({name ? name : "?", tx, ty, "coeff"});
         // this rank's columns of the box: grid columns r, r + G, ... < ty = columns 0 .. mine - 1 of the local table, and the same columns
-        // of the coefficient matrix (distributed: its own local columns; replicated: that column set is cut out first).  world = 1: the
-        // whole box, strides = the matrices' own.
+        // of the coefficient matrix (distributed: its own local columns; replicated: that column set is cut out first, and the cut is the
+        // batch's to keep).  world = 1: the whole box, strides = the matrices' own.
         const size_t mine = shard_.cols_of(ty);
         const ScalarField *scalars = poly.poly.ptr();
         size_t scalar_stride = poly.ly();
         if (shard_.world > 1 && poly.rep) {
             DensePolynomialExt d = poly.to_distributed();
             scalar_stride = d.ly();
-            poly.commit_slice_ = std::move(d.poly);
-            scalars = poly.commit_slice_.ptr();
+            scalars = batch.keep(std::move(d.poly));
         }
         tkmk_msm_job_ex j{};
         j.scalars = scalars;
@@ -1119,46 +1274,19 @@ class Sigma1 {
         // large commits through the expanded table; small ones (the wide windows' two-pass sort needs 2^18 entries, and a 2^19-bucket
         // reduction is not worth paying for a few thousand points) through level 0 with the ordinary multi-window path
         if (table_c_ && (uint64_t)tx * mine * table_factor_ >= (1ull << 20)) use_table(j);
-        return j;
-    }
-    static G1Affine to_affine(const tkmk_g1_projective &res) {
-        G1Affine out{};
-        bool inf = true;
-        for (uint32_t l : res.z.limbs) inf &= l == 0;
-        if (!inf) out.x = res.x, out.y = res.y;  // canonical (x, y, 1): dropping z is G1Affine::from(projective)
-        return out;
-    }
-    static tkmk_msm_config device_cfg() {
-        tkmk_msm_config cfg = tkmk_msm_default_config();
-        cfg.are_scalars_on_device = cfg.are_points_on_device = true;
-        return cfg;
-    }
-    // independent MSM jobs over converted tables in one pipelined call -> affine results; (0,0) = G1serde::zero()
-    // stream: the caller's stream for the batch's scratch frame (a helper thread names its own, so that its frame does not share the
-    // default stream's arena with the main thread: tkmk.h "re-entrant per stream")
-    static std::vector<G1Affine> run_jobs(const std::vector<tkmk_msm_job_ex> &jobs, tkmk_stream stream = nullptr) {
-        tkmk_msm_config cfg = device_cfg();
-        cfg.stream_handle = stream;
-        std::vector<tkmk_g1_projective> res(jobs.size());
-        if (host_trace_on()) {
-            std::string d;
-            for (auto &j : jobs) d += " " + std::to_string(j.msm_size) + (j.table_c ? "t" : "") + (j.base_index ? "i" : "");
-            host_trace("commit batch of %zu:%s", jobs.size(), d.c_str());
-        }
-        const CommitComm &cc = commit_comm();
-        if (cc.comm) check(cc.multi_ex_sharded(cc.comm, jobs.data(), (int)jobs.size(), &cfg, TKMK_BASES_ACC_READY, res.data()), "tkmk_msm_multi_ex_sharded");
-        else check(tkmk_msm_multi_ex(jobs.data(), (int)jobs.size(), &cfg, TKMK_BASES_ACC_READY, res.data()), "tkmk_msm_multi_ex");
-        std::vector<G1Affine> out;
-        for (auto &r : res) out.push_back(to_affine(r));
-        return out;
+        batch.add(j);
     }
     // -> affine commitment
-    G1Affine encode_poly(DensePolynomialExt &poly, const char *name = nullptr) const { return run_jobs({job(poly, name)})[0]; }
-    // the MSM job of a polynomial given by its EVALUATIONS on the grid of this table, which holds the Lagrange-basis points of that grid
+    G1Affine encode_poly(DensePolynomialExt &poly, const char *name = nullptr) const {
+        CommitBatch batch;
+        job(batch, poly, name);
+        return batch.run()[0];
+    }
+    // adds the MSM job of a polynomial given by its EVALUATIONS on the grid of this table, which holds the Lagrange-basis points of that grid
     // (lagrange_of below): every row of the table against the evaluation vector, no view; zeros and small values cost the MSM next to
     // nothing.  Sharded prover: the table object is built over THIS RANK'S part of the grid (its columns, or its stretch of the walk) and
     // `evals` is the same part of the evaluations — COLS layout on both sides.
-    tkmk_msm_job_ex job_evals(const DeviceVec<ScalarField> &evals, const char *name = nullptr, size_t whole_x = 0, size_t whole_y = 0) const {
+    void job_evals(CommitBatch &batch, const DeviceVec<ScalarField> &evals, const char *name = nullptr, size_t whole_x = 0, size_t whole_y = 0) const {
         if (shard_.world != 1) throw Error("job_evals: a Lagrange-basis table is built over the rank's own part of the grid");
         if (evals.len() < rs_x_ * rs_y_) throw Error("evaluation vector shorter than the Lagrange table");
         if (auto *sink = commit_box_sink()) sink->push_back({name ? name : "?", whole_x ? whole_x : rs_x_, whole_y ? whole_y : rs_y_, "evals"});
@@ -1168,7 +1296,7 @@ class Sigma1 {
         j.msm_size = (int)(rs_x_ * rs_y_);
         j.base_table_len = table_len();
         if (table_c_ && (uint64_t)rs_x_ * rs_y_ * table_factor_ >= (1ull << 20)) use_table(j);
-        return j;
+        batch.add(j);
     }
     // The Lagrange-basis twin of the grid [0, xs) x [0, ys) of this table: [L_i(tau_x) L_j(tau_y)] G = (1 / N) x the inverse NTT over G1
     // points of the monomial sub-grid (tkmk_g1_ntt is unscaled; tkmk_g1_scale folds the 1 / N in, once per circuit), with the same commit
@@ -1199,9 +1327,9 @@ class Sigma1 {
     }
     // commitments of independent polynomials in one pipelined call
     std::vector<G1Affine> encode_polys(const std::vector<DensePolynomialExt *> &polys, const std::vector<const char *> &names = {}) const {
-        std::vector<tkmk_msm_job_ex> jobs;
-        for (size_t k = 0; k < polys.size(); k++) jobs.push_back(job(*polys[k], k < names.size() ? names[k] : nullptr));
-        return run_jobs(jobs);
+        CommitBatch batch;
+        for (size_t k = 0; k < polys.size(); k++) job(batch, *polys[k], k < names.size() ? names[k] : nullptr);
+        return batch.run();
     }
 };
 

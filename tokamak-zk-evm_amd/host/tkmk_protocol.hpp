@@ -118,13 +118,6 @@ struct SetupParams {
     size_t l, l_user_out, l_user, l_free, l_D, m_D, n, s_D, s_max;
 };
 
-inline G1Affine projective_to_affine(const tkmk_g1_projective &r) {
-    G1Affine out{};
-    bool inf = true;
-    for (uint32_t l : r.z.limbs) inf &= l == 0;
-    if (!inf) out.x = r.x, out.y = r.y;
-    return out;
-}
 // msm_g1_bases over rows `idx` of a device-resident table
 inline G1Affine msm_gathered(const DeviceVec<G1Affine> &table, const std::vector<uint32_t> &idx, const std::vector<ScalarField> &scalars) {
     if (idx.size() != scalars.size()) throw Error("msm input length mismatch");

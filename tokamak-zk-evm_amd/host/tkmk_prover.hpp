@@ -149,12 +149,9 @@ inline CrsRootVerdict identify_crs_root(const G1Affine *grid_dev, int bases_form
     uint32_t in_effect = 0;
     check(tkmk_ntt_root_generator(&in_effect), "tkmk_ntt_root_generator");
     std::vector<uint32_t> cand;
-    bool pinned = false;
-    if (const char *e = std::getenv("TKMK_FR_ROOT_GENERATOR")) {
-        const int v = std::atoi(e);
-        if (v >= 2 && v < 65536) pinned = true, cand.push_back((uint32_t)v);
-    }
-    if (!pinned) {
+    const uint32_t pinned = pinned_root_generator();
+    if (pinned) cand.push_back(pinned);
+    else {
         cand.push_back(in_effect);
         for (uint32_t g : {5u, 7u})
             if (g != in_effect) cand.push_back(g);
@@ -168,18 +165,11 @@ inline CrsRootVerdict identify_crs_root(const G1Affine *grid_dev, int bases_form
     check(tkmk_crs_identify_root(grid_dev, bases_form, (uint32_t)rs_x, (uint32_t)rs_y, (uint32_t)m_i, (uint32_t)sp.s_max, dc.on() ? dc.r() : 0u, (uint32_t)G,
                                  cand.data(), (int)C, mine.data()),
           "tkmk_crs_identify_root");
-    auto affine_of = [](const tkmk_g1_projective &res) {   // canonical (x, y, 1) / (0, 1, 0): dropping z is G1Affine::from(projective)
-        G1Affine out{};
-        bool inf = true;
-        for (uint32_t l : res.z.limbs) inf &= l == 0;
-        if (!inf) out.x = res.x, out.y = res.y;
-        return out;
-    };
     std::vector<G1Affine> sums(C);
-    for (size_t c = 0; c < C; c++) sums[c] = affine_of(mine[c]);
+    for (size_t c = 0; c < C; c++) sums[c] = projective_to_affine(mine[c]);
     if (G > 1) {   // rank-major partials of every rank -> per candidate the sum over the ranks (a host-operand MSM batch of G unit terms each)
         std::vector<G1Affine> all(C * G), pts(C * G);
-        check(dc.all_gather_host(dc.comm, sums.data(), C * sizeof(G1Affine), all.data()), "tkmk_comm_all_gather_host");
+        check(dc.link->all_gather_host(dc.link->comm, sums.data(), C * sizeof(G1Affine), all.data()), "tkmk_comm_all_gather_host");
         for (size_t c = 0; c < C; c++)
             for (size_t r = 0; r < G; r++) pts[c * G + r] = all[r * C + c];
         std::vector<ScalarField> ones(C * G, fr_from_u32(1));
@@ -187,7 +177,7 @@ inline CrsRootVerdict identify_crs_root(const G1Affine *grid_dev, int bases_form
         hc.batch_size = (int)C, hc.are_points_shared_in_batch = false;
         std::vector<tkmk_g1_projective> res(C);
         check(bls12_381_msm(ones.data(), pts.data(), (int)G, &hc, res.data()), "sum of the ranks' partials");
-        for (size_t c = 0; c < C; c++) sums[c] = affine_of(res[c]);
+        for (size_t c = 0; c < C; c++) sums[c] = projective_to_affine(res[c]);
     }
     std::vector<uint32_t> match;
     for (size_t c = 0; c < C; c++)
@@ -467,15 +457,14 @@ class Prover {
             const char *e = getenv("TKMK_PROVER_EARLY_COMMITS");
             return !(e && atoi(e) == 0);
         }();
-        return enabled && commit_stream && !dist_ctx().on() && !commit_comm().comm && !commit_box_sink() && tkmk_msm_get_pipeline_streams() > 1;
+        return enabled && commit_stream && !dist_ctx().installed() && !commit_box_sink() && tkmk_msm_get_pipeline_streams() > 1;
     }
     // background: the batch's accumulate kernels take one workgroup per CU (tkmk_stream_set_background) — for a dense commit nothing waits
     // for until the end of the round (prove4's M_X under the round's polynomial work: 54.4 -> 52.2 ms); prove0's evaluation commits are what
     // the round ends on and stay foreground (measured: background costs them 1 ms)
-    std::future<std::vector<G1Affine>> commit_early(std::vector<tkmk_msm_job_ex> jobs, bool background = false) const {
-        tkmk_stream st = commit_stream;
-        check(tkmk_stream_set_background(st, background ? 1 : 0), "tkmk_stream_set_background");
-        return std::async(std::launch::async, [jobs, st] { return Sigma1::run_jobs(jobs, st); });
+    CommitBatch::Pending commit_early(CommitBatch &&batch, bool background = false) const {
+        check(tkmk_stream_set_background(commit_stream, background ? 1 : 0), "tkmk_stream_set_background");
+        return std::move(batch).start(commit_stream);
     }
     // The blinding points of the evaluation-basis commitments: commit(p + sum_k c_k T^k (T^e - 1)) = MSM(evaluations of p, Lagrange table)
     // + sum_k c_k ([tau^(e+k)]G - [tau^k]G), and the second summand depends on the mixer and the CRS only — one small batched MSM per
@@ -643,10 +632,13 @@ class Prover {
         size_t n = sp.n, s_max = sp.s_max;
         const bool from_evaluations = lagrange_n && lagrange_mi && u_ev.len() && v_ev.len() && w_ev.len() && b_ev.len();
         // the evaluation-basis commits need nothing this round computes: they start now, under the transforms of p0 and its division
-        std::future<std::vector<G1Affine>> early;
-        if (from_evaluations && can_commit_early())
-            early = commit_early({lagrange_n->job_evals(u_ev, "U", n, s_max), lagrange_n->job_evals(v_ev, "V", n, s_max), lagrange_n->job_evals(w_ev, "W", n, s_max),
-                                  lagrange_mi->job_evals(b_ev, "B", m_i, s_max)});
+        CommitBatch::Pending early;
+        if (from_evaluations && can_commit_early()) {
+            CommitBatch uvwb;
+            lagrange_n->job_evals(uvwb, u_ev, "U", n, s_max), lagrange_n->job_evals(uvwb, v_ev, "V", n, s_max), lagrange_n->job_evals(uvwb, w_ev, "W", n, s_max);
+            lagrange_mi->job_evals(uvwb, b_ev, "B", m_i, s_max);
+            early = commit_early(std::move(uvwb));
+        }
         Poly p0XY = uXY * vXY - wXY;
         auto q01 = p0XY.div_by_vanishing_opt((int64_t)n, (int64_t)s_max);
         q0XY = std::move(q01.first), q1XY = std::move(q01.second);
@@ -671,17 +663,20 @@ class Prover {
     // U, V, W, B from the evaluations (same points as the coefficient route above):
     //   commit(p + sum_k c_k T^k (T^e - 1)) = MSM(evaluations of p, Lagrange table) + sum_k c_k ([tau^(e+k)]G - [tau^k]G)
     // early (valid): the four evaluation commits were issued before the round's polynomial work and are collected here
-    Proof0 prove0_from_evaluations(Poly &Q_AX_XY, Poly &Q_AY_XY, std::future<std::vector<G1Affine>> &early) {
+    Proof0 prove0_from_evaluations(const Poly &Q_AX_XY, const Poly &Q_AY_XY, CommitBatch::Pending &early) {
         using namespace prover_detail;
         const size_t n = sp.n, s_max = sp.s_max;
         std::vector<G1Affine> c(6);
+        CommitBatch batch;
         if (early.valid()) {
-            std::vector<G1Affine> q = Sigma1::run_jobs({sigma->sigma1.job(Q_AX_XY, "Q_AX"), sigma->sigma1.job(Q_AY_XY, "Q_AY")});
+            sigma->sigma1.job(batch, Q_AX_XY, "Q_AX"), sigma->sigma1.job(batch, Q_AY_XY, "Q_AY");
+            std::vector<G1Affine> q = batch.run();
             std::vector<G1Affine> e = early.get();
             c = {e[0], e[1], e[2], q[0], q[1], e[3]};
         } else {
-            c = Sigma1::run_jobs({lagrange_n->job_evals(u_ev, "U", n, s_max), lagrange_n->job_evals(v_ev, "V", n, s_max), lagrange_n->job_evals(w_ev, "W", n, s_max),
-                                  sigma->sigma1.job(Q_AX_XY, "Q_AX"), sigma->sigma1.job(Q_AY_XY, "Q_AY"), lagrange_mi->job_evals(b_ev, "B", m_i, s_max)});
+            lagrange_n->job_evals(batch, u_ev, "U", n, s_max), lagrange_n->job_evals(batch, v_ev, "V", n, s_max), lagrange_n->job_evals(batch, w_ev, "W", n, s_max);
+            sigma->sigma1.job(batch, Q_AX_XY, "Q_AX"), sigma->sigma1.job(batch, Q_AY_XY, "Q_AY"), lagrange_mi->job_evals(batch, b_ev, "B", m_i, s_max);
+            c = batch.run();
         }
         // the Lagrange tables carry the transform's 1 / N (tkmk_g1_scale at open): the MSM is the commitment of the unblinded polynomial
         const Blinds &bl = blinds();
@@ -736,7 +731,7 @@ class Prover {
             pc.batch_size = (int)lc;
             check(bls12_381_vector_product(tr.ptr(), m_i, &pc, totals.ptr()), "vector_product");
             std::vector<ScalarField> mine = totals.to_host(), all((size_t)G * lc);
-            check(dc.all_gather_host(dc.comm, mine.data(), lc * sizeof(ScalarField), all.data()), "tkmk_comm_all_gather_host");
+            check(dc.link->all_gather_host(dc.link->comm, mine.data(), lc * sizeof(ScalarField), all.data()), "tkmk_comm_all_gather_host");
             auto total_of = [&](size_t col) { return all[(col % G) * lc + col / G]; };
             std::vector<ScalarField> others(lc, fr_one());   // O_k
             for (size_t k = 0; k < lc; k++)
@@ -756,7 +751,7 @@ class Prover {
             DeviceVec<ScalarField> tops(lc);
             check(tkmk_memcpy_2d_d2d(tops.ptr(), sizeof(ScalarField), sfx.ptr(), m_i * sizeof(ScalarField), sizeof(ScalarField), lc), "gather column tops");
             std::vector<ScalarField> my_tops = tops.to_host(), all_tops((size_t)G * lc);
-            check(dc.all_gather_host(dc.comm, my_tops.data(), lc * sizeof(ScalarField), all_tops.data()), "tkmk_comm_all_gather_host");
+            check(dc.link->all_gather_host(dc.link->comm, my_tops.data(), lc * sizeof(ScalarField), all_tops.data()), "tkmk_comm_all_gather_host");
             next_top.assign(lc, ScalarField{});
             for (size_t k = 0; k < lc; k++) {
                 const size_t col = r + G * k + 1;
@@ -781,7 +776,9 @@ class Prover {
                 compact.copy_from_host(ends.data(), lc);
                 check(tkmk_memcpy_2d_d2d(d.ptr() + (m_i - 1), m_i * sizeof(ScalarField), compact.ptr(), sizeof(ScalarField), sizeof(ScalarField), lc), "scatter column ends");
             }
-            G1Affine core = Sigma1::run_jobs({lagrange_mi_prefix->job_evals(d, "R", m_i * s_max, 1)})[0];
+            CommitBatch batch;
+            lagrange_mi_prefix->job_evals(batch, d, "R", m_i * s_max, 1);
+            G1Affine core = batch.run()[0];
             return Proof1{fqh::g1_affine_add(core, blinds().R)};
         }
         Poly RXY = blinded_R();
@@ -890,9 +887,12 @@ class Prover {
         const Poly m_R = constant_poly(fr_neg(proof3.R_eval)), m_V = constant_poly(fr_neg(proof3.V_eval));
         auto M = minus_constant(R_lin, m_R_wx).div_by_ruffini(chi_w, zeta);
         auto N = minus_constant(R_lin, m_R_wxy).div_by_ruffini(chi_w, zeta_w);
-        std::future<std::vector<G1Affine>> early;   // declared after M and N: it ends (and is waited for) before the polynomials its jobs read
-        if (!test_parts && can_commit_early())
-            early = commit_early({sigma->sigma1.job(std::get<0>(M), "M_X"), sigma->sigma1.job(std::get<1>(M), "M_Y"), sigma->sigma1.job(std::get<1>(N), "N_Y")}, true);
+        CommitBatch::Pending early;   // borrows M and N: declared after them
+        if (!test_parts && can_commit_early()) {
+            CommitBatch openings;
+            sigma->sigma1.job(openings, std::get<0>(M), "M_X"), sigma->sigma1.job(openings, std::get<1>(M), "M_Y"), sigma->sigma1.job(openings, std::get<1>(N), "N_Y");
+            early = commit_early(std::move(openings), true);
+        }
 
         // Pi_A: arithmetic constraints + the opening of V (lib.rs:2383-2532); t_n(chi) = chi^n - 1, t_smax(zeta) = zeta^s_max - 1
         const ScalarField t_n_eval = fr_sub(fr_pow(chi, n), one), t_smax_eval = fr_sub(fr_pow(zeta, s_max), one), small_v_eval = ev(vXY);

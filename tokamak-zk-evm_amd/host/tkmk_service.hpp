@@ -30,55 +30,14 @@ namespace tkmk {
 // column of u, v, w, b, s0, s1); a rank commits its columns of every polynomial against its columns of the table, and the shares of a
 // round's commitments meet in ONE all-gather.  Replicated: the host's parse of the three documents, the Fiat-Shamir transcript (every rank
 // derives the same challenges from the same commitments, so the rounds need no message) and the few small polynomials built from host
-// values.  The entries of libtkmk_dist.so arrive as function pointers (the prover library does not link RCCL).
-struct ShardLink {
-    void *comm = nullptr;
-    Shard shard;
-    tkmk_error (*multi_ex_sharded)(void *, const tkmk_msm_job_ex *, int, const tkmk_msm_config *, int, tkmk_g1_projective *) = nullptr;
-    tkmk_error (*broadcast_host)(void *, void *, size_t, int) = nullptr;
-    tkmk_error (*device_turn)(void *, int) = nullptr;
-    tkmk_error (*all_gather_host)(void *, const void *, size_t, void *) = nullptr;
-    tkmk_error (*agree)(void *, tkmk_error) = nullptr;
-    tkmk_error (*abort)(void *) = nullptr;
-    tkmk_error (*fwd_cols_to_rows)(void *, const tkmk_fr *, size_t, size_t, size_t, size_t, int, tkmk_fr *) = nullptr;
-    tkmk_error (*inv_rows_to_cols)(void *, tkmk_fr *, size_t, size_t, int, tkmk_fr *) = nullptr;
-    tkmk_error (*rows_rotate)(void *, const tkmk_fr *, size_t, size_t, size_t, tkmk_fr *) = nullptr;
-    tkmk_error (*ring_shift)(void *, const void *, size_t, int, void *) = nullptr;
-    tkmk_error (*relayout_cols_to_rows)(void *, const void *, size_t, size_t, size_t, void *) = nullptr;
-    tkmk_error (*relayout_rows_to_cols)(void *, const void *, size_t, size_t, size_t, void *) = nullptr;
-    explicit operator bool() const { return comm != nullptr; }
-};
-// for the span of one call on a sharded context: this thread's polynomials are distributed (dist_ctx()), its commit batches go through the
-// communicator, and (loopback transport only) this virtual rank holds the device turn except while it waits for its peers
-struct ShardSpan {
-    const ShardLink &link;
-    explicit ShardSpan(const ShardLink &l) : link(l) {
-        if (!link) return;
-        check(link.device_turn(link.comm, 1), "tkmk_comm_device_turn");
-        commit_comm() = CommitComm{link.comm, link.multi_ex_sharded};
-        DistCtx &dc = dist_ctx();
-        dc.comm = link.comm, dc.shard = link.shard;
-        dc.all_gather_host = link.all_gather_host, dc.fwd_cols_to_rows = link.fwd_cols_to_rows, dc.inv_rows_to_cols = link.inv_rows_to_cols;
-        dc.rows_rotate = link.rows_rotate, dc.ring_shift = link.ring_shift;
-    }
-    ~ShardSpan() {
-        if (!link) return;
-        dist_ctx() = DistCtx{};
-        commit_comm() = CommitComm{};
-        (void)link.device_turn(link.comm, 0);
-    }
-};
+// values.  The entries of libtkmk_dist.so arrive as function pointers (the prover library does not link RCCL): ShardLink of
+// host/tkmk_host.hpp, and every call on a sharded context runs under a ShardSpan of the context's link.
 
 // The four binding commitments of Prover::init (A_free, O_pub_free, O_mid, O_prv: lib.rs:1086-1160) enter the proof document but not the
 // transcript: no round waits for them.  On a single-GPU context their MSM batch is issued from a helper thread on its own stream as
 // soon as the routed witness lists exist, and collected after prove4: its sort and tail kernels (latency-bound, a few ms) then run under
-// prove0's transforms and streaming passes instead of in front of them.  Members are destroyed in reverse order: the future first
-// (it waits for the batch), the operand buffers after it.
-struct PendingBinding {
-    DeviceVec<ScalarField> mid_sc, prv_sc, pub_sc;
-    DeviceVec<uint32_t> mid_ix, prv_ix, pub_ix;
-    std::future<std::vector<G1Affine>> cores;   // A_free, O_pub_free, O_mid_core, O_prv_core
-};
+// prove0's transforms and streaming passes instead of in front of them.  The batch (A_free, O_pub_free, O_mid_core, O_prv_core) owns the
+// routed lists; the handle that runs it is a CommitBatch::Pending.
 
 struct ProveTiming {   // seconds
     double parse = 0, upload = 0, build = 0, binding = 0, init = 0;
@@ -115,7 +74,7 @@ class ProverContext {
     std::unique_ptr<Sigma1> lagrange_mi_prefix_;                      // prefix sums of the m_I x s_max one in prove1's walk order
     const Sigma1 *lagrange_mi_ = nullptr;                             // (= lagrange_n_ when n == m_I)
 
-    tkmk_stream binding_stream_ = nullptr;                          // the helper thread's stream (PendingBinding)
+    tkmk_stream binding_stream_ = nullptr;                          // the helper thread's stream (the pending binding batch)
     tkmk_stream commit_stream_ = nullptr;                           // the stream of a round's early commits (Prover::commit_early)
     ScalarField *pinned_ = nullptr;                                 // witness staging
     uint64_t pinned_cap_ = 0;
@@ -344,11 +303,11 @@ class ProverContext {
                             j.scalars = ones.ptr(), j.bases = walk.ptr() + k * m_i, j.msm_size = (int)m_i, j.base_table_len = m_i;
                             jobs[k] = j;
                         }
-                        tkmk_msm_config mc = Sigma1::device_cfg();
+                        tkmk_msm_config mc = msm_dev_cfg();
                         std::vector<tkmk_g1_projective> tot(lc);
                         check(tkmk_msm_multi_ex(jobs.data(), (int)lc, &mc, TKMK_BASES_PLAIN, tot.data()), "column totals");
                         std::vector<G1Affine> mine(lc), all(lc * G);
-                        for (size_t k = 0; k < lc; k++) mine[k] = Sigma1::to_affine(tot[k]);
+                        for (size_t k = 0; k < lc; k++) mine[k] = projective_to_affine(tot[k]);
                         check(lk.all_gather_host(lk.comm, mine.data(), lc * sizeof(G1Affine), all.data()), "tkmk_comm_all_gather_host");
                         auto total_of = [&](size_t col) { return all[(col % G) * lc + col / G]; };
                         std::vector<G1Affine> between(lc, G1Affine{});   // (0, 0) = the point at infinity
@@ -363,7 +322,7 @@ class ProverContext {
                             hc.batch_size = (int)lc, hc.are_points_shared_in_batch = false;
                             std::vector<tkmk_g1_projective> res(lc);
                             check(bls12_381_msm(sc.data(), pts.data(), (int)(G - 1), &hc, res.data()), "sums between my columns");
-                            for (size_t k = 0; k < lc; k++) between[k] = Sigma1::to_affine(res[k]);
+                            for (size_t k = 0; k < lc; k++) between[k] = projective_to_affine(res[k]);
                         }
                         DeviceVec<G1Affine> seq(lc * (m_i + 1)), sums(lc * (m_i + 1)), pre(lc * m_i);
                         for (size_t k = 0; k < lc; k++) {
@@ -398,9 +357,9 @@ class ProverContext {
     }
 
     // Prover::init (prove/src/lib.rs:675-1206) from the synthesizer's directory
-    // pending (optional): when given and this context is not sharded, the binding batch is left running and *pending holds it;
-    // finish_binding() completes the returned Binding later.  Otherwise the Binding is complete on return.
-    std::pair<std::unique_ptr<Prover>, Binding> init(const std::string &synth_dir, const Mixer &mixer, ProveTiming &tm, std::unique_ptr<PendingBinding> *pending = nullptr) {
+    // pending (optional): when given and this context is not sharded, the binding batch is left running and *pending holds it (it borrows
+    // the returned prover's a_free_X); finish_binding() completes the returned Binding later.  Otherwise the Binding is complete on return.
+    std::pair<std::unique_ptr<Prover>, Binding> init(const std::string &synth_dir, const Mixer &mixer, ProveTiming &tm, CommitBatch::Pending *pending = nullptr) {
         using namespace prover_detail;
         const double t0 = Prover::now();
         const size_t n = sp.n, s_max = sp.s_max, K = infos.size();
@@ -609,14 +568,11 @@ class ProverContext {
         const Mixer &mx = mixer;
         Binding b;
         // sharded: the binding tables are replicated and a rank commits the (scalar, row) lists of its own placements
-        auto indexed = [](const DeviceVec<ScalarField> &sc, const DeviceVec<uint32_t> &ix, uint64_t cnt, const DeviceVec<G1Affine> &table) {
-            tkmk_msm_job_ex j{};
-            j.scalars = sc.ptr(), j.bases = table.ptr(), j.msm_size = (int)cnt, j.base_index = ix.ptr(), j.base_table_len = table.len();
-            return j;
-        };
-        std::vector<tkmk_msm_job_ex> binding_jobs = {sigma->sigma1.job(p->a_free_X, "A_free"), indexed(pub_sc, pub_ix, n_pub, sigma->gamma_inv_o_inst),
-                                                     indexed(mid_sc, mid_ix, n_mid, sigma->eta_inv_li_o_inter_alpha4_kj),
-                                                     indexed(prv_sc, prv_ix, n_prv, sigma->delta_inv_li_o_prv)};
+        CommitBatch binding;
+        sigma->sigma1.job(binding, p->a_free_X, "A_free");
+        binding.add_indexed(std::move(pub_sc), std::move(pub_ix), n_pub, sigma->gamma_inv_o_inst);
+        binding.add_indexed(std::move(mid_sc), std::move(mid_ix), n_mid, sigma->eta_inv_li_o_inter_alpha4_kj);
+        binding.add_indexed(std::move(prv_sc), std::move(prv_ix), n_prv, sigma->delta_inv_li_o_prv);
         static const bool async_binding = [] {
             const char *e = getenv("TKMK_PROVER_ASYNC_BINDING");
             return !(e && atoi(e) == 0);
@@ -624,26 +580,19 @@ class ProverContext {
         // (at one pipeline stream — bench.py's serialised profiling pass: every kernel alone on the device — the batch runs in line)
         if (pending && !link && async_binding && tkmk_msm_get_pipeline_streams() > 1) {
             if (!binding_stream_) check(tkmk_stream_create(&binding_stream_), "stream_create");
-            pending->reset(new PendingBinding());
-            PendingBinding &pb = **pending;
-            pb.mid_sc = std::move(mid_sc), pb.prv_sc = std::move(prv_sc), pb.pub_sc = std::move(pub_sc);   // the jobs point into these blocks
-            pb.mid_ix = std::move(mid_ix), pb.prv_ix = std::move(prv_ix), pb.pub_ix = std::move(pub_ix);
             tkmk_stream bs = binding_stream_;
             // the helper first makes the proof's blinding points (one small MSM + a host Horner, 2 ms: prove0 needs them at its END, the
             // binding commitments are needed after prove4), then runs the binding batch
             std::shared_ptr<std::promise<void>> blinds_done = std::make_shared<std::promise<void>>();
             p->blinds_ready = blinds_done->get_future().share();
-            Prover *pp = p.get();   // alive until this future has been collected (ProverContext::prove: `pending` goes before the prover)
-            pb.cores = std::async(std::launch::async, [binding_jobs, bs, pp, blinds_done] {
-                if (blinds_done) {
-                    try {
-                        pp->blinds_.reset(new Prover::Blinds(pp->compute_blinds(bs)));
-                        blinds_done->set_value();
-                    } catch (...) {
-                        blinds_done->set_exception(std::current_exception());
-                    }
+            Prover *pp = p.get();   // borrowed like a_free_X: alive until *pending has ended (ProverContext::prove)
+            *pending = std::move(binding).start(bs, [bs, pp, blinds_done] {
+                try {
+                    pp->blinds_.reset(new Prover::Blinds(pp->compute_blinds(bs)));
+                    blinds_done->set_value();
+                } catch (...) {
+                    blinds_done->set_exception(std::current_exception());
                 }
-                return Sigma1::run_jobs(binding_jobs, bs);
             });
             tm.binding = Prover::now() - t3;
             tm.init = Prover::now() - t0;
@@ -651,7 +600,7 @@ class ProverContext {
             p->timing["init.binding"] = tm.binding, p->timing["init.total"] = tm.init;
             return {std::move(p), b};
         }
-        b = finish_binding(Sigma1::run_jobs(binding_jobs), p->blinds());
+        b = finish_binding(binding.run(), p->blinds());
         tm.binding = Prover::now() - t3;
         tm.init = Prover::now() - t0;
         p->timing["init.parse"] = tm.parse, p->timing["init.upload"] = tm.upload, p->timing["init.build"] = tm.build;
@@ -681,7 +630,7 @@ class ProverContext {
         static_assert(std::is_trivially_copyable<Mixer>::value, "Mixer travels as bytes");
         if (link) check(link.broadcast_host(link.comm, &mixer, sizeof mixer, 0), "tkmk_comm_broadcast_host");
         std::pair<std::unique_ptr<Prover>, Binding> pb;
-        std::unique_ptr<PendingBinding> pending;   // declared after pb: destroyed (and thereby waited for) BEFORE the prover whose a_free_X it reads
+        CommitBatch::Pending pending;   // borrows the prover's a_free_X: declared after pb
         std::map<std::string, double> times;
         Proof proof;
         try {
@@ -689,7 +638,7 @@ class ProverContext {
             if (flags & 2) pb.first->lagrange_n = pb.first->lagrange_mi = pb.first->lagrange_mi_prefix = nullptr;
             proof = run_rounds(*pb.first, pb.second, &times, (flags & 1) != 0);
         } catch (const Error &e) {
-            if (pending && pending->cores.valid()) pending->cores.wait();   // the batch reads a_free_X of the prover about to go
+            pending.wait();   // before the prover goes, and before the peers are told
             // A rank that leaves between two collectives must not leave its peers waiting in the next one.  What the replicated inputs
             // decide — a malformed document, a shape that does not fit (invalid argument / pointer) — fails every rank at the same point
             // and the communicator lives on; a failure only this rank may have had (memory, a device or transport error) aborts it.
@@ -697,14 +646,14 @@ class ProverContext {
             if (link && link.shard.world > 1 && !replicated_cause) (void)link.abort(link.comm);
             throw;
         } catch (...) {
-            if (pending && pending->cores.valid()) pending->cores.wait();
+            pending.wait();
             if (link && link.shard.world > 1) (void)link.abort(link.comm);
             throw;
         }
-        if (pending) {   // collect the binding commitments issued during init
+        if (pending.valid()) {   // collect the binding commitments issued during init
             const double tb = Prover::now();
-            proof.binding = finish_binding(pending->cores.get(), pb.first->blinds());
-            pending.reset();
+            proof.binding = finish_binding(pending.get(), pb.first->blinds());
+            pending = CommitBatch::Pending();   // the routed lists go here
             tm.binding += Prover::now() - tb;
         }
         int k = 0;

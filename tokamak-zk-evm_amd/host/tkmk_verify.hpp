@@ -93,10 +93,7 @@ struct Report {
 // ---- the generator in effect, and roots of unity on the host ----
 inline uint32_t generator_in_effect(uint32_t explicit_generator = 0) {
     if (explicit_generator) return explicit_generator;
-    if (const char *e = std::getenv("TKMK_FR_ROOT_GENERATOR")) {   // the rule of the device library (csrc/ntt_impl.inc)
-        const int v = std::atoi(e);
-        if (v >= 2 && v < 65536) return (uint32_t)v;
-    }
+    if (const uint32_t pinned = pinned_root_generator()) return pinned;
     return TKMK_BLS12_381_FR_ROOT_GENERATOR;
 }
 inline ScalarField fr_pow_wide(const ScalarField &a, const frh::U256 &e) {
