@@ -691,6 +691,12 @@ tkmk_error tkmk_diag_bench(int kind, uint32_t iters, uint32_t blocks, int reps, 
 tkmk_error tkmk_diag_gather_probe(const void *table_dev, uint32_t row_bytes, const uint32_t *idx_dev, uint64_t n, int reps, float *ms_out);
 /* out[i] = a[i]*b[i] through the device Montgomery product; field 0 = Fr (32 B), 1 = Fq (48 B); device pointers */
 tkmk_error tkmk_diag_field_mul(int field, const void *a_dev, const void *b_dev, void *out_dev, uint64_t n);
+/* the unsaturated base-field products of the MSM accumulate loop (csrc/ffu.h) on RAW limb operands, one lane per tuple: curve 0 =
+ * BLS12-381 Fq (14 limbs of 29 bits), 1 = BN254 Fq (10 x 28); op 0 = mul(a, b), 1 = mul_add(a, b, c, d), 2 = mul_add with c a
+ * neg2_unswept() value (limbs below 2^(W+1)), 3 = sqr(a).  a..d, out: n x L uint32 limbs on the device, no conversion on either
+ * side; operands an op does not read may be NULL.  The caller keeps the operand bounds of ffu.h (nothing is checked on the device). */
+tkmk_error tkmk_diag_ffu(int curve, int op, const uint32_t *a_dev, const uint32_t *b_dev, const uint32_t *c_dev, const uint32_t *d_dev, uint32_t *out_dev,
+                         uint64_t n);
 
 #ifdef __cplusplus
 }

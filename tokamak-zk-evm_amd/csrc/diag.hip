@@ -66,7 +66,7 @@ __global__ __launch_bounds__(256) void k_diag(uint32_t iters, uint32_t *sink) {
         typename FU::E a = FU::one(), b = FU::one();
         a.l[0] ^= t & 0xffff;
         b.l[1] ^= 0x1234;
-        for (uint32_t i = 0; i < iters; i++) a = FU::mul(a, b);
+        for (uint32_t i = 0; i < iters; i++) a = FU::mul_portable(a, b);   // the experiment field has no generated column chains
         if (a.l[0] == 0x12345) sink[t] = a.l[1];
     } else if (KIND == 7) {   // one butterfly's worth in that form: product + add + sub (limb-wise, one carry sweep each)
         using FU = ffu<bls12_381_fr9_params>;
@@ -74,7 +74,7 @@ __global__ __launch_bounds__(256) void k_diag(uint32_t iters, uint32_t *sink) {
         a.l[0] ^= t & 0xffff;
         w.l[1] ^= 0x1234;
         for (uint32_t i = 0; i < iters; i++) {
-            typename FU::E m = FU::mul(b, w);
+            typename FU::E m = FU::mul_portable(b, w);
             typename FU::E s = FU::add(a, m);
             b = FU::template sub<2>(a, m);
             a = FU::cond_sub_p(FU::cond_sub_p(s));   // keep the chain bounded like a real pass would every few stages
@@ -275,6 +275,47 @@ TK_API tkmk_error tkmk_diag_field_mul(int field, const void *a_dev, const void *
     TK_HIP(hipGetLastError());
     TK_HIP(hipDeviceSynchronize());
     return TKMK_SUCCESS;
+}
+
+// out[i] = op(a[i], b[i], c[i], d[i]) on raw limbs through the unsaturated products of the accumulate loop (ffu.h): op 0 mul, 1 mul_add,
+// 2 mul_add<true> (c unswept), 3 sqr — lets the gpu test tier compare the device column chains limb for limb against the big-integer
+// definition of the result, on operands at the bounds the curve formulas reach (ec_u.h).
+template <class FU, int OP>
+__global__ __launch_bounds__(256) void k_diag_ffu(const typename FU::E *a, const typename FU::E *b, const typename FU::E *c, const typename FU::E *d,
+                                                  typename FU::E *out, uint64_t n) {
+    uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    typename FU::E r;
+    if (OP == 0) r = FU::mul(a[i], b[i]);
+    else if (OP == 1) r = FU::template mul_add<false>(a[i], b[i], c[i], d[i]);
+    else if (OP == 2) r = FU::template mul_add<true>(a[i], b[i], c[i], d[i]);
+    else r = FU::sqr(a[i]);
+    out[i] = r;
+}
+template <class FU>
+static tkmk_error diag_ffu_launch(int op, const uint32_t *a, const uint32_t *b, const uint32_t *c, const uint32_t *d, uint32_t *out, uint64_t n) {
+    using E = typename FU::E;
+    const E *ea = (const E *)a, *eb = (const E *)b, *ec = (const E *)c, *ed = (const E *)d;
+    E *eo = (E *)out;
+    uint32_t blocks = (uint32_t)tk_div_up(n, 256);
+    switch (op) {
+        case 0: hipLaunchKernelGGL((k_diag_ffu<FU, 0>), blocks, 256, 0, 0, ea, eb, ec, ed, eo, n); break;
+        case 1: hipLaunchKernelGGL((k_diag_ffu<FU, 1>), blocks, 256, 0, 0, ea, eb, ec, ed, eo, n); break;
+        case 2: hipLaunchKernelGGL((k_diag_ffu<FU, 2>), blocks, 256, 0, 0, ea, eb, ec, ed, eo, n); break;
+        default: hipLaunchKernelGGL((k_diag_ffu<FU, 3>), blocks, 256, 0, 0, ea, eb, ec, ed, eo, n); break;
+    }
+    TK_HIP(hipGetLastError());
+    TK_HIP(hipDeviceSynchronize());
+    return TKMK_SUCCESS;
+}
+TK_API tkmk_error tkmk_diag_ffu(int curve, int op, const uint32_t *a_dev, const uint32_t *b_dev, const uint32_t *c_dev, const uint32_t *d_dev, uint32_t *out_dev,
+                                uint64_t n) {
+    if (curve < 0 || curve > 1 || op < 0 || op > 3) return TKMK_ERR_INVALID_ARGUMENT;
+    TK_TRY(tk_require_device());
+    if (n == 0) return TKMK_SUCCESS;
+    if (!a_dev || !out_dev || (op != 3 && !b_dev) || ((op == 1 || op == 2) && (!c_dev || !d_dev))) return TKMK_ERR_INVALID_POINTER;
+    if (curve == 0) return diag_ffu_launch<ffu<bls12_381_fq_params>>(op, a_dev, b_dev, c_dev, d_dev, out_dev, n);
+    return diag_ffu_launch<ffu<bn254_fq_params>>(op, a_dev, b_dev, c_dev, d_dev, out_dev, n);
 }
 
 // ---- known-bytes gather probe: calibrates rocprofv3's FETCH_SIZE for the access pattern of k_accumulate_chunks ----

@@ -124,11 +124,28 @@ struct ffu {
 
     // Montgomery product a*b/2^(W L) mod p (redundant): strict operands, a*b < 2^20 p^2; strict result < 1.03 p.
     // Product scanning; a 64-bit column accumulator cannot overflow: 2L products < 2^58 plus a carry < 2^35.
+    //
+    // Device builds of mul / mul_add / sqr run the generated column chains of field_params.h (tools/gen_field_params.py:
+    // gen_unsat_products): the same columns, each summed into the ONE accumulator by asm multiply-adds whose addend is the carry of the
+    // column before.  From the portable loops below hipcc reassociates the column sum — it opens every next column in a second
+    // accumulator from 0 and joins the two with a 64-bit add per column, 26-27 v_lshl_add_u64 per product.  The host build is the
+    // portable code with every FFU_ASSERT (tests/hostcheck); tkmk_diag_ffu (diag.hip) checks the device chains limb for limb.
     static FF_HD E mul(const E &a, const E &b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        E r;
+        P::mulu_cols(a.l, b.l, r.l);
+        return r;
+#else
+        return mul_portable(a, b);
+#endif
+    }
+    // the product as portable C++ on either side.  On the device only the conversions at the edge of a kernel and in the degenerate
+    // path take it (to_sat_mont): with the chains there too, k_combine needs more than 256 registers and falls to one wave per SIMD.
+    static FF_HD E mul_portable(const E &a, const E &b) {
         FFU_ASSERT(strict(a) && strict(b) && a.l[L - 1] <= MASK && b.l[L - 1] <= MASK);
+        E r;
         uint32_t m[L];
         uint64_t acc = 0;
-        E r;
 #pragma unroll
         for (int k = 0; k < L; k++) {
 #pragma unroll
@@ -167,9 +184,12 @@ struct ffu {
         } else {
             FFU_ASSERT(strict(c) && c.l[L - 1] <= MASK);
         }
+        E r;
+#if defined(__HIP_DEVICE_COMPILE__)
+        P::mul_addu_cols(a.l, b.l, c.l, d.l, r.l);
+#else
         uint32_t m[L];
         uint64_t acc = 0;
-        E r;
 #pragma unroll
         for (int k = 0; k < L; k++) {
 #pragma unroll
@@ -195,16 +215,20 @@ struct ffu {
             acc >>= W;
         }
         r.l[L - 1] = (uint32_t)acc;
+#endif
         return r;
     }
     // a^2: off-diagonal products once against 2a (limbs < 2^30; column bound still below 2^63)
     static FF_HD E sqr(const E &a) {
         FFU_ASSERT(strict(a) && a.l[L - 1] <= MASK);
+        E r;
+#if defined(__HIP_DEVICE_COMPILE__)
+        P::sqru_cols(a.l, r.l);
+#else
         uint32_t m[L], a2[L];
 #pragma unroll
         for (int i = 0; i < L; i++) a2[i] = a.l[i] << 1;
         uint64_t acc = 0;
-        E r;
 #pragma unroll
         for (int k = 0; k < L; k++) {
 #pragma unroll
@@ -227,6 +251,7 @@ struct ffu {
             acc >>= W;
         }
         r.l[L - 1] = (uint32_t)acc;
+#endif
         return r;
     }
 
@@ -283,7 +308,7 @@ struct ffu {
         E c;
 #pragma unroll
         for (int i = 0; i < L; i++) c.l[i] = P::RSATU[i];
-        return pack(cond_sub_p(mul(a, c)));
+        return pack(cond_sub_p(mul_portable(a, c)));
     }
     // packed canonical x*2^(W L) (what k_convert_bases stores)  ->  strict
     static FF_HD E from_packed(const S &s) { return unpack(s); }

@@ -94,7 +94,7 @@ SYMBOLS = [
     "bls12_381_vector_mul", "bls12_381_vector_div", "bls12_381_vector_inv", "bls12_381_scalar_add_vec",
     "bls12_381_scalar_sub_vec", "bls12_381_scalar_mul_vec", "bls12_381_vector_sum", "bls12_381_vector_product",
     "bls12_381_matrix_transpose", "tkmk_vec_suffix_product", "tkmk_fr_random_device", "tkmk_gather_rows_device", "tkmk_g1_batch_scalar_mul_device", "tkmk_profile_enable",
-    "tkmk_profile_reset", "tkmk_profile_get", "tkmk_diag_bench", "tkmk_diag_field_mul", "tkmk_poly_find_degree",
+    "tkmk_profile_reset", "tkmk_profile_get", "tkmk_diag_bench", "tkmk_diag_field_mul", "tkmk_diag_ffu", "tkmk_poly_find_degree",
     "tkmk_poly_place", "tkmk_poly_scale_coeffs", "tkmk_poly_mul_x_minus_one_evals", "tkmk_poly_mul_ones_x", "tkmk_poly_expr_eval", "tkmk_poly_expr_eval_views", "tkmk_poly_expr_eval_views_slab", "tkmk_poly_eval_x", "tkmk_poly_eval_y", "tkmk_poly_eval",
     "tkmk_poly_div_by_vanishing_opt", "tkmk_poly_div_by_ruffini", "tkmk_r1cs_eval_rows",
     "tkmk_msm_multi_ex", "bls12_381_msm_convert_bases", "tkmk_r1cs_library_create", "tkmk_r1cs_library_destroy", "tkmk_r1cs_library_eval",
@@ -744,6 +744,28 @@ def diag_field_mul(field, a, b):
     do = DeviceBuffer(a.size)
     _check(lib().tkmk_diag_field_mul(int(field), _p(da), _p(db), _p(do), ctypes.c_uint64(a.size // width)), "tkmk_diag_field_mul")
     return do.to_host()
+
+
+FFU_LIMBS = {0: (14, 29), 1: (10, 28)}      # curve -> (limbs, bits per limb) of the unsaturated base field (csrc/ffu.h)
+FFU_MUL, FFU_MUL_ADD, FFU_MUL_ADD_UNSWEPT, FFU_SQR = 0, 1, 2, 3
+
+
+def diag_ffu(curve, op, a, b=None, c=None, d=None):
+    """the device's unsaturated products (csrc/ffu.h: mul, mul_add, mul_add<true>, sqr) on raw limbs: a..d are (n, L) uint32 arrays
+    (L = 14 for curve 0 = BLS12-381 Fq, 10 for curve 1 = BN254 Fq), one lane per row; returns the raw (n, L) result limbs"""
+    L = FFU_LIMBS[curve][0]
+    need = {FFU_MUL: 2, FFU_MUL_ADD: 4, FFU_MUL_ADD_UNSWEPT: 4, FFU_SQR: 1}[op]
+    ops = [a, b, c, d][:need]
+    if any(x is None for x in ops):
+        raise ValueError("diag_ffu: op %d reads %d operands" % (op, need))
+    ops = [np.ascontiguousarray(x, dtype=np.uint32) for x in ops]
+    n = ops[0].shape[0]
+    if any(x.shape != (n, L) for x in ops):
+        raise ValueError("diag_ffu: operands must be (n, %d) uint32" % L)
+    dev = [DeviceBuffer.from_host(x.view(np.uint8).reshape(-1)) for x in ops] + [None] * (4 - need)
+    do = DeviceBuffer(4 * L * n)
+    _check(lib().tkmk_diag_ffu(int(curve), int(op), *[_p(x) if x is not None else None for x in dev], _p(do), ctypes.c_uint64(n)), "tkmk_diag_ffu")
+    return do.to_host().view(np.uint32).reshape(n, L)
 
 
 def gather_rows_device(src, row_bytes, idx, out=None):

@@ -7,7 +7,8 @@ import os
 FIELDS = {
     # BLS12-381 (the reference's only curve: packages/backend/Cargo.toml:23)
     "bls12_381_fr": dict(mod=0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001, two_adicity=32, qnr=5, wu=28),
-    "bls12_381_fq": dict(mod=0x1A0111EA397FE69A4B1BA7B6434BACD764774B84F38512BF6730D2A0F6B0F6241EABFFFEB153FFFFB9FEFFFFFFFFAAAB),
+    # ucols: the field's ffu products run as generated column chains on the device (gen_unsat_products): the two base fields of the MSM
+    "bls12_381_fq": dict(mod=0x1A0111EA397FE69A4B1BA7B6434BACD764774B84F38512BF6730D2A0F6B0F6241EABFFFEB153FFFFB9FEFFFFFFFFAAAB, ucols=True),
     # BN254 (second instantiation named by BASELINE.json configs; no counterpart in the reference)
     # experiment: Fr with the tightest unsaturated form (9 x 29 bits = 261 bits, only 6 spare bits: operands must stay below
     # a few r; csrc/diag.hip kind 6 measures its product against the saturated one)
@@ -15,7 +16,7 @@ FIELDS = {
     "bn254_fr": dict(mod=21888242871839275222246405745257275088548364400416034343698204186575808495617, two_adicity=28, qnr=5, wu=28),
     # 28-bit limbs: with 29 the top limb of 2p would be empty (10 limbs start at bit 261 > 254) and the dominating-limb
     # subtraction constants of ffu::sub<K> need a non-zero top limb
-    "bn254_fq": dict(mod=21888242871839275222246405745257275088696311157297823662689037894645226208583, wu=28),
+    "bn254_fq": dict(mod=21888242871839275222246405745257275088696311157297823662689037894645226208583, wu=28, ucols=True),
 }
 
 
@@ -170,8 +171,99 @@ def gen_unsat(name, p, WU, L_override=None):
     return o
 
 
+MAX_UMADS = 14  # per asm statement of an unsaturated column: 1 + 2*14 = 29 operands
+
+
+def unsat_macros():
+    """instruction text and operand pairs of the column statements, once at the head of the file: TKU_MADS_n = n multiply-adds of operands
+    (1, 2) .. (2n - 1, 2n) into operand 0; TKU_ZMADS_n opens a product (literal-zero addend); TKU_CMADS_n(w) shifts the carry out after the first"""
+    o = ["#if defined(__HIP_DEVICE_COMPILE__)",
+         '#define TKU_M(i, j) "v_mad_u64_u32 %0, vcc, %" #i ", %" #j ", %0\\n\\t"',
+         '#define TKU_V(x, y) "v"(x), "v"(y)',
+         '#define TKU_P(x, i) "v"(x), "s"(MODU[i])',  # a limb of the modulus: a scalar register
+         '#define TKU_T_1 ""']
+    for n in range(2, MAX_UMADS + 1):
+        o.append("#define TKU_T_%d TKU_T_%d TKU_M(%d, %d)" % (n, n - 1, 2 * n - 1, 2 * n))
+    for n in range(1, MAX_UMADS + 1):
+        o.append("#define TKU_MADS_%d TKU_M(1, 2) TKU_T_%d" % (n, n))
+        o.append('#define TKU_ZMADS_%d "v_mad_u64_u32 %%0, vcc, %%1, %%2, 0\\n\\t" TKU_T_%d' % (n, n))
+        o.append('#define TKU_CMADS_%d(w) TKU_M(1, 2) "v_lshrrev_b64 %%0, " #w ", %%0\\n\\t" TKU_T_%d' % (n, n))
+    return o + ["#endif", ""]
+
+
+def gen_unsat_products(L, WU):
+    """Device-only column chains of ffu::mul / mul_add / sqr (csrc/ffu.h): every column adds all of its products into the ONE 64-bit
+    accumulator, the carry of a column being the addend of the next column's first v_mad_u64_u32.  Written as plain C++ the compiler
+    reassociates the column sum: it starts every next column in a second accumulator from 0 before the carry exists and joins the two
+    with one 64-bit add per column (26-27 v_lshl_add_u64 per product that the algorithm does not have).  A column is one asm statement
+    (two or three when it has more than MAX_UMADS products), not one statement per product: hipcc pads one wait state after an asm
+    statement whose output the next instruction reads, and in a single chain that is every statement.  The first multiply-add of a product
+    takes a literal-zero addend; the modulus limbs ride in scalar registers ("s" of a constant)."""
+    MASK = (1 << WU) - 1
+    o = []
+
+    def emit(L_, macs, first=False, close=None):
+        """one column.  close: the m[k] of the column before — its m[k] p0 and the carry shift open this column's statement (a statement
+        of their own would cost one more pad per column)"""
+        items = ([("s", close, "0")] if close else []) + macs
+        nch = -(-len(items) // MAX_UMADS)
+        per = -(-len(items) // nch)
+        for ci in range(nch):
+            chunk = items[ci * per:(ci + 1) * per]
+            # the instruction text is a macro of the file's head (UNSAT_MACROS): n multiply-adds on operands 1..2n, the first with a
+            # literal 0 (TKU_ZMADS) or followed by the carry shift (TKU_CMADS)
+            text = "TKU_ZMADS_%d" if first and ci == 0 else "TKU_CMADS_%d(%d)" % (len(chunk), WU) if close and ci == 0 else "TKU_MADS_%d"
+            text = text % len(chunk) if "%d" in text else text
+            ins = ", ".join(("TKU_V(%s,%s)" if kind == "v" else "TKU_P(%s,%s)") % (x, y) for kind, x, y in chunk)
+            L_.append('        asm(%s : "%s"(acc) : %s : "vcc");' % (text, "=v" if first and ci == 0 else "+v", ins))
+
+    def product(name, args, pre, col):
+        """col(k) -> the operand products (x, y) of column k, both in VGPRs"""
+        o.append("    static __device__ __forceinline__ void %s(%s, uint32_t *r) {" % (name, args))
+        o.append("        uint32_t m[%d];" % L)
+        o.append("        uint64_t acc;")
+        o.extend(pre)
+        close = None
+        for k in range(2 * L - 1):
+            macs = [("v", x, y) for x, y in col(k)]
+            for j in range(max(0, k - L + 1), min(k - 1, L - 1) + 1):
+                macs.append(("s", "m[%d]" % j, "%d" % (k - j)))
+            emit(o, macs, first=(k == 0), close=close)
+            close = None
+            if k < L:
+                o.append("        m[%d] = ((uint32_t)acc * INVU) & 0x%08xu;" % (k, MASK))
+                close = "m[%d]" % k
+            else:
+                o.append("        r[%d] = (uint32_t)acc & 0x%08xu;" % (k - L, MASK))
+                o.append("        acc >>= %d;" % WU)
+        o.append("        r[%d] = (uint32_t)acc;" % (L - 1))
+        o.append("    }")
+
+    def ab(k):
+        return [("a[%d]" % j, "b[%d]" % (k - j)) for j in range(max(0, k - L + 1), min(k, L - 1) + 1)]
+
+    def abcd(k):
+        out = []
+        for j in range(max(0, k - L + 1), min(k, L - 1) + 1):
+            out += [("a[%d]" % j, "b[%d]" % (k - j)), ("c[%d]" % j, "d[%d]" % (k - j))]
+        return out
+
+    def sq(k):   # off-diagonal products once against 2a
+        out = [("a2[%d]" % j, "a[%d]" % (k - j)) for j in range(max(0, k - L + 1), L) if 2 * j < k]
+        if k % 2 == 0:
+            out.append(("a[%d]" % (k // 2), "a[%d]" % (k // 2)))
+        return out
+
+    o.append("    // ---- ffu::mul / mul_add / sqr as single column chains (see tools/gen_field_params.py:gen_unsat_products) ----")
+    product("mulu_cols", "const uint32_t *a, const uint32_t *b", [], ab)
+    product("mul_addu_cols", "const uint32_t *a, const uint32_t *b, const uint32_t *c, const uint32_t *d", [], abcd)
+    product("sqru_cols", "const uint32_t *a", ["        uint32_t a2[%d];" % L, "#pragma unroll", "        for (int i = 0; i < %d; i++) a2[i] = a[i] << 1;" % L], sq)
+    return o
+
+
 def main():
     out = ["// GENERATED by tools/gen_field_params.py — do not edit.", "#pragma once", "#include <stdint.h>", ""]
+    out.extend(unsat_macros())
     for name, f in FIELDS.items():
         p = f["mod"]
         n = (p.bit_length() + 31) // 32
@@ -201,6 +293,9 @@ def main():
         out.append("    }")
         out.append("    // r = (r + b) mod p, r = (r - b) mod p for r, b < p;  r in [0,2p) -> [0,p)")
         out.extend(gen_linear(n, p))
+        if f.get("ucols"):
+            wu = f.get("wu", WU_DEFAULT)
+            out.extend(gen_unsat_products(f.get("lu") or -(-(p.bit_length() + 24) // wu), wu))
         out.append("#endif")
         out.append("};")
         out.append("")
