@@ -252,6 +252,30 @@ tkmk_error bls12_381_msm_convert_bases(const tkmk_g1_affine *bases, uint64_t n, 
  * (TKMK_ERR_INVALID_ARGUMENT otherwise), whatever cfg->are_results_on_device says; `bases` follows cfg->are_points_on_device. */
 tkmk_error bls12_381_msm_precompute_bases_acc(const tkmk_g1_affine *bases, uint64_t n, const tkmk_msm_config *cfg, void *out, uint64_t *out_bytes);
 
+/* Segmented small MSM: many independent, RAGGED sums of a few terms each over resident tables in TWO launches, whatever n_jobs is (the
+ * G1 linear combinations of a verifier's fold, of an audit's small tables): k_msm_segmented, one workgroup per (job, four 4-bit windows)
+ * with 64 term slots that walk the job's terms by double-and-add per digit, then the tail — Horner over the job's 64 window sums, the
+ * inversion, the canonical record — in k_msm_segmented_finish, one lane per job: no sort, no buckets, no host arithmetic, no copy to the
+ * host other than the results.  One lane's chain of ~250 dependent doublings takes 5 ms on this device whatever the number of jobs, so a
+ * SYNCHRONOUS call of at most 64 jobs runs the same tail on a few host threads instead (0.2 ms per job and thread), as bls12_381_msm does
+ * for its small batches; the bytes are the same.
+ * jobs / cfg / bases_form as tkmk_msm_multi_ex (operands on the device, cfg->batch_size == 1, base_index needs base_table_len, a strided
+ * box must lie inside its table, an index >= base_table_len is clamped before the read and makes the call return
+ * TKMK_ERR_INVALID_ARGUMENT), and results[j] is byte for byte what tkmk_msm_multi_ex returns for job j.  Refused with
+ * TKMK_ERR_INVALID_ARGUMENT: a job with table_c != 0 or table_factor != 0, bases_form == TKMK_BASES_ACC_READY, and a job of more than
+ * TKMK_MSM_SEGMENTED_MAX_SIZE terms (double-and-add per digit costs ~2.5 group operations per term and window where the bucket method
+ * costs one: above a few hundred terms the sorting pipeline is the faster entry).  cfg->c is not used.
+ * cfg->are_results_on_device: `results` is a device array of n_jobs records, written by the finish kernel itself.  With cfg->is_async as
+ * well the call returns without synchronising cfg->stream_handle; an out-of-range index can then not be reported by the call: it is
+ * recorded for the stream and reported — once — by tkmk_msm_segmented_status(stream), which waits for the stream and returns
+ * TKMK_ERR_INVALID_ARGUMENT if any asynchronous tkmk_msm_segmented call on that stream since the last query clamped an index (the results
+ * of such a call mean nothing), TKMK_SUCCESS otherwise.  A synchronous call reports its own indices itself and leaves no record.
+ * Work counters: "msm.segmented_jobs" and "msm.segmented_terms" ("msm.points" / "msm.calls" do not count these jobs); profile sections
+ * "msm.segmented" and "msm.segmented_finish". */
+#define TKMK_MSM_SEGMENTED_MAX_SIZE 4096   /* terms per job */
+tkmk_error tkmk_msm_segmented(const tkmk_msm_job_ex *jobs, int n_jobs, const tkmk_msm_config *cfg, int bases_form, tkmk_g1_projective *results);
+tkmk_error tkmk_msm_segmented_status(tkmk_stream stream);
+
 /* Which root of unity was this reference string made under?  The CRS carries lagrange_KL = [L_{s_max-1}(tau_y) K_{m_I-1}(tau_x)] G
  * (libs/src/group_structures/mod.rs:326-327), and L_{n-1}(X) = (1/n) sum_j w_n^j X^j, so
  *     lagrange_KL = sum_{a < m_i} sum_{b < s_max} (w_x^a / m_i) (w_y^b / s_max) xy_powers[a * rs_y + b]
@@ -668,10 +692,11 @@ tkmk_error tkmk_host_free(void *ptr);
  * Measurement hooks (no reference counterpart; the reference's `timing` feature wraps host spans:
  * libs/src/lib.rs:11-141).  When enabled, launchers bracket each kernel with HIP events recorded on the
  * launch stream; names: "msm.digits|hist|scan|scatter|accumulate|reduce_segments|reduce_windows|
- * convert_bases", "ntt.pass<k>", "g1.check".  Recording does not wait for anything (the pipelined MSM entry keeps its overlap);
+ * convert_bases|segmented|segmented_finish", "ntt.pass<k>", "g1.check".  Recording does not wait for anything (the pipelined MSM entry keeps its overlap);
  * tkmk_profile_get waits for the recorded events and returns the section's summed time and launch count.
  * tkmk_stats_*: what the library was asked to do since the last reset — "msm.points", "msm.calls", "ntt.elements",
- * "ntt.calls" — for the algorithmic-byte figures of the roofline report (128 B per point, 64 B per element).
+ * "ntt.calls" — for the algorithmic-byte figures of the roofline report (128 B per point, 64 B per element); "msm.segmented_jobs" and
+ * "msm.segmented_terms" count what tkmk_msm_segmented was given, apart from the former.
  * --------------------------------------------------------------------------------------------- */
 /* Independent MSMs of one tkmk_msm_multi[_ex] call run round-robin on n internal streams (default 3, environment TKMK_MSM_STREAMS;
  * 1..8; 0 restores the default).  n = 1 issues every kernel of the batch in order on one stream: no two kernels of the batch

@@ -155,13 +155,14 @@ tkmk_error tkmk_prover_verify(tkmk_prover *p, const char *synthesizer_dir, const
  *               once.  Sigma2 is checked once; an all-zero Sigma2, a bad G2 point or one at infinity makes every item false with that reason.
  *   route       the caller's choice, no hidden size threshold.  TKMK_VERIFY_ROUTE_HOST: pure host work on TKMK_HOST_THREADS threads, no
  *               device call.  TKMK_VERIFY_ROUTE_DEVICE: the records are uploaded once, ONE tkmk_g1_check call does the membership pass and
- *               ONE tkmk_msm_multi_ex call per fold the ten sums (host/tkmk_verify_device.hpp); the pairing stays on the host.  It runs on
+ *               one tkmk_msm_segmented call per fold (and one tkmk_msm_multi_ex call for the slot jobs too long for it) the ten sums
+ *               (host/tkmk_verify_device.hpp; the report counts both: "segmented_jobs", "pipeline_jobs"); the pairing stays on the host.  It runs on
  *               the default stream in its own buffers, takes turns with the prover contexts of the process, and reads and changes no
  *               library or context state (NTT domain, generator in effect, commit tables).  Without a device: TKMK_ERR_NO_DEVICE.  For
- *               one or a few items the device route is SLOWER than the host route.
+ *               ONE item the two routes cost the same; from a few items on the device route is the faster one.
  *   errors      n = 0 is TKMK_ERR_INVALID_ARGUMENT (a vacuous "all true" does not exist); a document that cannot be read or parsed is an
  *               error whose message names the item index and the file, and no verdict is given.
- * report_json_out (optional, tkmk_prover_free_string): {"generator", "ok", "n", "route": "host" | "device", "products", "items": [one
+ * report_json_out (optional, tkmk_prover_free_string): {"generator", "ok", "n", "route": "host" | "device", "products", "segmented_jobs", "pipeline_jobs", "items": [one
  * report of tkmk_verify_files per item], "seconds": {"parse", "membership", "fold", "pairings", "total"}}.
  * NOT covered: batches across different reference strings or circuits, BN254, a device route for sharded contexts. */
 typedef struct {

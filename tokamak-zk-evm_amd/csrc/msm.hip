@@ -7,6 +7,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <thread>
 #include <vector>
 
 #include "common.h"
@@ -28,4 +29,6 @@
 #define TK_MSM_ABI_JOB_EX tkmk_msm_job_ex
 #define TK_MSM_SYM_MULTI_EX tkmk_msm_multi_ex
 #define TK_MSM_SYM_CONVERT bls12_381_msm_convert_bases
+#define TK_MSM_SYM_SEGMENTED tkmk_msm_segmented   // BLS12-381 G1 only: the segmented small-MSM kernels have no BN254 twin
+#define TK_MSM_SYM_SEGMENTED_STATUS tkmk_msm_segmented_status
 #include "msm_impl.inc"

@@ -1031,6 +1031,112 @@ __global__ __launch_bounds__(256) void k_msm_small(const fr_t *__restrict__ scal
     if (i == 0) tk_store(reinterpret_cast<g1k_xyzz *>(out) + (uint64_t)b * SM_NW + w, acc);
 }
 
+#ifdef TK_MSM_SYM_SEGMENTED
+// SEGMENTED small MSM (tkmk_msm_segmented): the same work item as k_msm_small — (4-bit window w, term i) is digit_w(s_i) * P_i by
+// double-and-add — for MANY jobs of DIFFERENT sizes over views and index lists of resident tables, and with the tail on the device too.
+// One descriptor per job, built on the host and uploaded once per call; terms are addressed as tkmk_msm_job_ex addresses them.
+struct seg_job_t {
+    const fr_t *scalars;
+    const g1_affine_t *bases;
+    const uint32_t *index;      // base_index list (takes precedence over the base view), or nullptr
+    uint32_t n;                 // terms
+    uint32_t s_cols, s_stride;  // scalar view, 0 = contiguous
+    uint32_t b_cols, b_stride;  // base view, 0 = contiguous
+    uint32_t limit;             // records behind `bases` for an index list: an entry at or past it is clamped to 0 and flagged
+};
+__device__ __forceinline__ uint32_t seg_strided(uint32_t k, uint32_t cols, uint32_t stride) {
+    if (!cols) return k;
+    const uint32_t row = k / cols;
+    return row * stride + (k - row * cols);
+}
+// the slots a job can fill: min(n, 64) rounded up to a power of two (0 terms: 1)
+__host__ __device__ __forceinline__ uint32_t seg_slots(uint32_t n) {
+    uint32_t m = 1;
+    while (m < n && m < 64) m <<= 1;
+    return m;
+}
+// grid (jobs, 16): jobs on blockIdx.x (no 65 535 limit), blockIdx.y = a group of four windows; 256 lanes = 4 windows x 64 term slots.
+// Slot `slot` walks terms slot, slot + 64, ... of its job (ragged: 129 terms are three trips, 0 terms none).  Dynamic LDS: 4 x lds_slots
+// XYZZ records, lds_slots = the widest seg_slots() of the call; a call of one-term jobs takes none and does no LDS addition.  The tree
+// uses the complete addition: equal points meet in it whenever a record occurs twice in a job.  out[job][w] = sum_i digit_w(s_i) P_i.
+__global__ __launch_bounds__(256) void k_msm_segmented(const seg_job_t *__restrict__ jobs, int form, fq_t conv, int scalars_mont, uint32_t bits,
+                                                      uint32_t lds_slots, uint32_t *__restrict__ flag, g1_xyzz_t *__restrict__ out) {
+    extern __shared__ uint4 seg_lds[];
+    const uint32_t t = threadIdx.x, slot = t & 63u, w = blockIdx.y * 4 + (t >> 6);
+    const seg_job_t jb = jobs[blockIdx.x];
+    // only the low `bits` bits of a scalar count (cfg->bitsize), as in k_msm_small
+    const uint32_t dmask = 4 * w >= bits ? 0u : 4 * w + 4 > bits ? (1u << (bits - 4 * w)) - 1u : 15u;
+    g1k_xyzz acc = G1K::inf();
+    for (uint32_t i = slot; i < jb.n; i += 64) {
+        uint32_t r = jb.index ? jb.index[i] : seg_strided(i, jb.b_cols, jb.b_stride);
+        if (jb.limit && r >= jb.limit) {   // whatever the digit is: every window reports the same indices
+            atomicOr(flag, 1u);
+            r = 0;
+        }
+        if (!dmask) continue;
+        fr_t s = Fr::canon(tk_load(jb.scalars + seg_strided(i, jb.s_cols, jb.s_stride)));
+        if (scalars_mont) s = Fr::from_mont(s);
+        uint32_t limb = 0;   // s.l[w >> 3] by selects: a runtime-indexed limb array would live in scratch
+#pragma unroll
+        for (uint32_t k = 0; k < 8; k++) limb = (w >> 3) == k ? s.l[k] : limb;
+        const uint32_t d = (limb >> ((w & 7u) * 4)) & dmask;
+        if (!d) continue;
+        const g1_affine_t p0 = tk_load(jb.bases + r);
+        if (G1::is_inf(p0)) continue;
+        g1k_aff p;
+        p.x = Fq::canon(p0.x), p.y = Fq::canon(p0.y);
+        if (form == TKMK_BASES_PLAIN) p.x = Fq::to_mont(p.x), p.y = Fq::to_mont(p.y);
+        else if (form == TKMK_BASES_CONVERTED) p.x = Fq::mul(p.x, conv), p.y = Fq::mul(p.y, conv);   // x R' * (R^2 / R') / R = x R
+        g1k_xyzz term = G1K::inf();
+#pragma unroll 1
+        for (int bit = 3; bit >= 0; bit--) {
+            term = G1K::dbl(term);
+            if ((d >> bit) & 1u) term = G1K::add_mixed(term, p);
+        }
+        acc = G1K::add(acc, term);
+    }
+    const uint32_t m = seg_slots(jb.n);   // the same in every lane of the workgroup: the barriers below are uniform
+    if (m > 1) {
+        g1k_xyzz *sh = reinterpret_cast<g1k_xyzz *>(seg_lds) + (t >> 6) * lds_slots;
+        if (slot < m) sh[slot] = acc;
+        __syncthreads();
+        for (uint32_t st = m >> 1; st > 0; st >>= 1) {
+            if (slot < st) {
+                acc = G1K::add(acc, sh[slot + st]);
+                sh[slot] = acc;
+            }
+            __syncthreads();
+        }
+    }
+    if (slot == 0) tk_store(reinterpret_cast<g1k_xyzz *>(out) + (uint64_t)blockIdx.x * SM_NW + w, acc);
+}
+// The tail, one lane per job: Horner over the job's window sums (4 doublings and one addition per window; windows at or past `nw` hold
+// nothing under cfg->bitsize), to_affine, and the library's canonical projective record — (x, y, 1), or (0, 1, 0) for infinity — what
+// store_canonical writes on the host.  `results` is device memory; dword stores, since a caller's record array need not be 16-byte aligned.
+__global__ __launch_bounds__(64) void k_msm_segmented_finish(const g1_xyzz_t *__restrict__ wins, uint32_t n_jobs, uint32_t nw, abi_proj *__restrict__ results) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n_jobs) return;
+    const g1k_xyzz *win = reinterpret_cast<const g1k_xyzz *>(wins) + (uint64_t)j * SM_NW;
+    g1k_xyzz acc = G1K::inf();
+#pragma unroll 1
+    for (int w = (int)nw - 1; w >= 0; w--) {
+#pragma unroll 1
+        for (int k = 0; k < 4; k++) acc = G1K::dbl(acc);
+        acc = G1K::add(acc, tk_load(win + w));
+    }
+    const bool inf = G1K::is_inf(acc);
+    const g1k_aff a = G1K::to_affine(acc);
+    const fq_t x = Fq::from_mont(a.x), y = Fq::from_mont(a.y);   // to_affine(infinity) = (0, 0)
+    uint32_t *o = reinterpret_cast<uint32_t *>(results + j);
+#pragma unroll
+    for (int i = 0; i < Fq::N; i++) {
+        o[i] = x.l[i];
+        o[Fq::N + i] = inf ? (i == 0 ? 1u : 0u) : y.l[i];
+        o[2 * Fq::N + i] = !inf && i == 0 ? 1u : 0u;
+    }
+}
+#endif
+
 // ---------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------
@@ -1539,7 +1645,13 @@ static msm_pipe_set &msm_pipe_set_of(hipStream_t caller) {
 
 // tkmk_stream_destroy (runtime.hip): the set that served a caller stream goes with it (its streams, events and pinned buffers; the scratch
 // arenas of its streams stay parked like every arena until tkmk_release_scratch)
+#ifdef TK_MSM_SYM_SEGMENTED
+static void seg_drop_stream_flag(hipStream_t s);   // the stream's out-of-range word of asynchronous segmented calls, if it has one
+#endif
 void drop_pipe_set(hipStream_t caller) {
+#ifdef TK_MSM_SYM_SEGMENTED
+    seg_drop_stream_flag(caller);
+#endif
     std::unique_ptr<msm_pipe_set> set;
     {
         std::lock_guard<std::mutex> lk(g_pipe_sets_mu);
@@ -1931,6 +2043,163 @@ TK_API tkmk_error TK_MSM_SYM_CONVERT(const abi_affine *bases, uint64_t n, const 
     TK_TRY(O.copy_back(out, (size_t)n * AFF_BYTES, cfg->are_results_on_device, s));
     TK_HIP(hipStreamSynchronize(s));
     return TKMK_SUCCESS;
+}
+#endif
+
+#ifdef TK_MSM_SYM_SEGMENTED
+// calls of at most this many jobs finish on the host (see TK_MSM_SYM_SEGMENTED): below the measured crossover of the two tails
+#define SEG_HOST_TAIL_MAX_JOBS 64
+#define SEG_HOST_TAIL_THREADS 8   // host threads of that tail (one job is one serial chain)
+// The out-of-range record of ASYNCHRONOUS segmented calls: one resident device word per caller stream that made such a call, set by the
+// kernel, read and cleared by TK_MSM_SYM_SEGMENTED_STATUS.  A synchronous call keeps its flag in its own frame.  Nothing else is kept.
+static std::mutex g_seg_flags_mu;
+static std::map<hipStream_t, uint32_t *> g_seg_flags;
+static uint32_t *seg_stream_flag(hipStream_t s, bool create) {
+    std::lock_guard<std::mutex> lk(g_seg_flags_mu);
+    auto it = g_seg_flags.find(s);
+    if (it != g_seg_flags.end()) return it->second;
+    if (!create) return nullptr;
+    uint32_t *p = nullptr;
+    if (hipMalloc((void **)&p, 4) != hipSuccess) return nullptr;
+    if (hipMemset(p, 0, 4) != hipSuccess) {
+        (void)hipFree(p);
+        return nullptr;
+    }
+    g_seg_flags[s] = p;
+    return p;
+}
+static void seg_drop_stream_flag(hipStream_t s) {   // tkmk_stream_destroy, through drop_pipe_set
+    std::lock_guard<std::mutex> lk(g_seg_flags_mu);
+    auto it = g_seg_flags.find(s);
+    if (it == g_seg_flags.end()) return;
+    (void)hipFree(it->second);
+    g_seg_flags.erase(it);
+}
+
+// Many ragged few-term MSMs over views / index lists of resident tables in two launches (k_msm_segmented, k_msm_segmented_finish); the
+// argument rules are TK_MSM_SYM_MULTI_EX's, results[j] its bytes.  Takes the caller's stream; reads and changes no library state (the
+// asynchronous form leaves its out-of-range word, see above).
+TK_API tkmk_error TK_MSM_SYM_SEGMENTED(const abi_job_ex *jobs, int n_jobs, const tkmk_msm_config *cfg, int bases_form, abi_proj *results) {
+    if (!cfg || cfg->ext || cfg->batch_size != 1 || n_jobs < 0 || cfg->precompute_factor > 1) return TKMK_ERR_INVALID_ARGUMENT;
+    if (bases_form != TKMK_BASES_PLAIN && bases_form != TKMK_BASES_MONTGOMERY && bases_form != TKMK_BASES_CONVERTED) return TKMK_ERR_INVALID_ARGUMENT;
+    if (cfg->bitsize < 0 || cfg->bitsize > 255 || cfg->c < 0 || cfg->c > MSM_MAX_C) return TKMK_ERR_INVALID_ARGUMENT;
+    if (!cfg->are_scalars_on_device || !cfg->are_points_on_device) return TKMK_ERR_INVALID_ARGUMENT;   // views address resident tables
+    if (n_jobs == 0) return TKMK_SUCCESS;
+    if (!jobs || !results) return TKMK_ERR_INVALID_POINTER;
+    TK_TRY(tk_require_device());
+    const uint32_t bits = cfg->bitsize ? (uint32_t)cfg->bitsize : (uint32_t)TK_MSM_SCALAR_BITS;
+    std::vector<seg_job_t> desc((size_t)n_jobs);
+    uint64_t terms = 0;
+    uint32_t lds_slots = 1;
+    for (int j = 0; j < n_jobs; j++) {
+        const abi_job_ex &jb = jobs[j];
+        if (jb.msm_size < 0 || jb.msm_size > TKMK_MSM_SEGMENTED_MAX_SIZE) return TKMK_ERR_INVALID_ARGUMENT;
+        if (jb.msm_size > 0 && (!jb.scalars || !jb.bases)) return TKMK_ERR_INVALID_POINTER;
+        if ((jb.scalar_cols && jb.scalar_stride < jb.scalar_cols) || (jb.base_cols && jb.base_stride < jb.base_cols)) return TKMK_ERR_INVALID_ARGUMENT;
+        if (jb.table_c != 0 || jb.table_factor != 0) return TKMK_ERR_INVALID_ARGUMENT;   // no table jobs here
+        const uint32_t n = (uint32_t)jb.msm_size;
+        // the box must lie inside the table it is cut from
+        if (n > 0 && jb.base_cols && !jb.base_index && jb.base_table_len) {
+            uint64_t last = (uint64_t)(n - 1) / jb.base_cols * jb.base_stride + (n - 1) % jb.base_cols;
+            if (last >= jb.base_table_len) return TKMK_ERR_INVALID_ARGUMENT;
+        }
+        if (jb.base_table_len >= (1ull << 31)) return TKMK_ERR_INVALID_ARGUMENT;
+        if (n > 0 && jb.base_index && !jb.base_table_len) return TKMK_ERR_INVALID_ARGUMENT;   // an index list is never gathered unchecked
+        desc[j] = seg_job_t{(const fr_t *)jb.scalars, (const g1_affine_t *)jb.bases, jb.base_index, n, jb.scalar_cols, jb.scalar_stride,
+                            jb.base_index ? 0u : jb.base_cols, jb.base_index ? 0u : jb.base_stride, jb.base_index ? (uint32_t)jb.base_table_len : 0u};
+        terms += n;
+        lds_slots = std::max(lds_slots, seg_slots(n));
+    }
+    hipStream_t s = tk_stream(cfg->stream_handle);
+    const bool on_dev = cfg->are_results_on_device, async = on_dev && cfg->is_async;
+    tk_frame frame(s);
+    tk_scratch d_desc, d_wins, d_flag, d_res;
+    TK_TRY(d_desc.alloc(desc.size() * sizeof(seg_job_t), s));
+    TK_TRY(d_wins.alloc((size_t)n_jobs * SM_NW * sizeof(g1_xyzz_t), s));
+    uint32_t *flag = nullptr;
+    if (async) {
+        flag = seg_stream_flag(s, true);
+        if (!flag) return TKMK_ERR_UNKNOWN;
+    } else {
+        TK_TRY(d_flag.alloc(4, s));
+        flag = d_flag.as<uint32_t>();
+        TK_HIP(hipMemsetAsync(flag, 0, 4, s));
+    }
+    // The tail of a SMALL call runs on the host: one lane's chain of 4 * nw doublings, nw additions and an inversion takes 5.5 ms on this
+    // device however few lanes run it (profiles/msm_segmented.json), the host's 64-bit limbs take 0.2 ms per job and thread, over a few
+    // threads.  The asynchronous form has no host in its path and always takes the device tail.
+    const bool host_tail = !async && n_jobs <= SEG_HOST_TAIL_MAX_JOBS;
+    abi_proj *d_out = results;
+    if (!on_dev && !host_tail) {
+        TK_TRY(d_res.alloc((size_t)n_jobs * sizeof(abi_proj), s));
+        d_out = d_res.as<abi_proj>();
+    }
+    // pageable source: the copy has left the host vector when this returns (as tk_staged::in relies on for every staged input)
+    TK_HIP(hipMemcpyAsync(d_desc.p, desc.data(), desc.size() * sizeof(seg_job_t), hipMemcpyHostToDevice, s));
+    fq_t rp;
+    for (int j = 0; j < Fq::N; j++) rp.l[j] = FqP::KSATM[j];   // R' mod p of the converted form, a plain integer
+    const fq_t conv = Fq::mul(Fq::inv(Fq::to_mont(rp)), Fq::r2());   // as csrc/g1check.hip: x R' * conv / R = x R
+    tk_prof prof(s);
+    hipLaunchKernelGGL(k_msm_segmented, dim3((uint32_t)n_jobs, SM_NW / 4), 256, lds_slots > 1 ? (size_t)4 * lds_slots * sizeof(g1k_xyzz) : 0, s,
+                       d_desc.as<seg_job_t>(), bases_form, conv, cfg->are_scalars_montgomery_form ? 1 : 0, bits, lds_slots, flag, d_wins.as<g1_xyzz_t>());
+    TK_HIP(hipGetLastError());
+    prof.mark("msm.segmented");
+    const uint32_t nw = (bits + 3) / 4;   // windows that can hold anything under cfg->bitsize
+    if (!host_tail) {
+        hipLaunchKernelGGL(k_msm_segmented_finish, tk_div_up((size_t)n_jobs, 64), 64, 0, s, d_wins.as<g1_xyzz_t>(), (uint32_t)n_jobs, nw, d_out);
+        TK_HIP(hipGetLastError());
+        prof.mark("msm.segmented_finish");
+    }
+    prof.finish();
+    tk_stat_add(TK_STAT_MSM_SEGMENTED_JOBS, (uint64_t)n_jobs);
+    tk_stat_add(TK_STAT_MSM_SEGMENTED_TERMS, terms);
+    if (async) return TKMK_SUCCESS;   // the stream orders the caller's next use of `results`; out-of-range indices: TK_MSM_SYM_SEGMENTED_STATUS
+    uint32_t h_flag = 0;
+    TK_HIP(hipMemcpyAsync(&h_flag, flag, 4, hipMemcpyDeviceToHost, s));
+    if (host_tail) {
+        std::vector<g1_xyzz_t> wins((size_t)n_jobs * SM_NW);
+        TK_HIP(hipMemcpyAsync(wins.data(), d_wins.p, wins.size() * sizeof(g1_xyzz_t), hipMemcpyDeviceToHost, s));
+        TK_HIP(hipStreamSynchronize(s));
+        if (h_flag) return TKMK_ERR_INVALID_ARGUMENT;
+        std::vector<abi_proj> host_res((size_t)n_jobs);
+        auto tail = [&](int first, int step) {   // jobs first, first + step, ...: independent chains of ~0.2 ms each
+            for (int j = first; j < n_jobs; j += step) {
+                g1_xyzz_t acc = G1::inf();
+                for (int w = (int)nw - 1; w >= 0; w--) {
+                    for (int k = 0; k < 4; k++) acc = G1::dbl(acc);
+                    acc = G1::add(acc, wins[(size_t)j * SM_NW + w]);
+                }
+                store_canonical(&host_res[j], acc);
+            }
+        };
+        const int workers = std::min(n_jobs, SEG_HOST_TAIL_THREADS);
+        std::vector<std::thread> pool;
+        for (int t = 1; t < workers; t++) pool.emplace_back(tail, t, workers);
+        tail(0, workers);
+        for (std::thread &t : pool) t.join();
+        if (on_dev) {
+            TK_HIP(hipMemcpyAsync(results, host_res.data(), host_res.size() * sizeof(abi_proj), hipMemcpyHostToDevice, s));
+            TK_HIP(hipStreamSynchronize(s));
+        } else {
+            for (int j = 0; j < n_jobs; j++) results[j] = host_res[j];
+        }
+        return TKMK_SUCCESS;
+    }
+    if (!on_dev) TK_HIP(hipMemcpyAsync(results, d_out, (size_t)n_jobs * sizeof(abi_proj), hipMemcpyDeviceToHost, s));
+    TK_HIP(hipStreamSynchronize(s));
+    return h_flag ? TKMK_ERR_INVALID_ARGUMENT : TKMK_SUCCESS;   // a base_index entry pointed past base_table_len (the read was clamped, not faulted)
+}
+TK_API tkmk_error TK_MSM_SYM_SEGMENTED_STATUS(tkmk_stream stream) {
+    hipStream_t s = tk_stream(stream);
+    uint32_t *flag = seg_stream_flag(s, false);
+    if (!flag) return TKMK_SUCCESS;   // no asynchronous segmented call was made on this stream
+    uint32_t h_flag = 0;
+    TK_HIP(hipMemcpyAsync(&h_flag, flag, 4, hipMemcpyDeviceToHost, s));
+    if (hipStreamSynchronize(s) != hipSuccess) return TKMK_ERR_UNKNOWN;
+    if (!h_flag) return TKMK_SUCCESS;
+    TK_HIP(hipMemsetAsync(flag, 0, 4, s));
+    TK_HIP(hipStreamSynchronize(s));
+    return TKMK_ERR_INVALID_ARGUMENT;
 }
 #endif
 

@@ -232,8 +232,8 @@ TKP_API tkmk_error tkmk_prover_verify(tkmk_prover *p, const char *synthesizer_di
 }
 
 // ---- batch verification (verify_batch of host/tkmk_verify.hpp; the device route is host/tkmk_verify_device.hpp) ----
-// route HOST: pure host work, as the three entries above.  route DEVICE: upload, one tkmk_g1_check, one tkmk_msm_multi_ex per fold on the
-// default stream, so it takes the unsharded contexts' turn, as the audit does.
+// route HOST: pure host work, as the three entries above.  route DEVICE: upload, one tkmk_g1_check, per fold one tkmk_msm_segmented and / or one
+// tkmk_msm_multi_ex call on the default stream, so it takes the unsharded contexts' turn, as the audit does.
 static void batch_entry(const char *entry, const verify::Inputs &shared, const tkmk_verify_item *items, size_t n, uint32_t generator, int route,
                         std::unique_ptr<verify::Sigma2> *sigma2_cache, uint8_t *ok_each, int *ok_all, char **report_json_out) {
     if (n == 0) throw Error(std::string(entry) + ": an empty batch has no verdict (n must be at least 1)");

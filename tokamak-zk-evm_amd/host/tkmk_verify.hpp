@@ -464,6 +464,8 @@ struct Folder {
     virtual void membership(const std::vector<tkmk_g1_affine> &records, std::vector<uint8_t> &verdict) = 0;
     // out[j] = sum_t slot[j][t].scalar * records[slot[j][t].record]; only records that passed membership are named
     virtual void fold(const std::vector<tkmk_g1_affine> &records, const std::vector<FoldTerm> (&slot)[kSlots], tkmk_g1_affine (&out)[kSlots]) = 0;
+    // slot jobs a device fold gave to the segmented small-MSM entry / to the sorting pipeline, summed over the folds (the host route: 0, 0)
+    uint64_t segmented_jobs = 0, pipeline_jobs = 0;
 };
 inline const char *g1_verdict_words(uint8_t v) {   // the words of pairing::g1_check for a verdict byte
     return v & TKMK_G1_BAD_NONCANONICAL ? "has a coordinate that is not reduced (>= p)" : v & TKMK_G1_BAD_OFF_CURVE ? "is not on the curve" : v ? "is not in the subgroup of order r" : "";
@@ -518,6 +520,7 @@ struct BatchReport {
     bool ok = false;            // every item is true
     std::string route;
     uint64_t products = 0;      // pairing products computed
+    uint64_t segmented_jobs = 0, pipeline_jobs = 0;   // the device route's slot jobs by MSM entry, over all folds of the call (Folder)
     std::vector<Report> items;
     double parse_s = 0, membership_s = 0, fold_s = 0, pairings_s = 0, total_s = 0;
     std::string to_json() const {
@@ -527,7 +530,8 @@ struct BatchReport {
             return std::string(b);
         };
         std::string d = "{\"generator\": " + std::to_string(generator) + ", \"ok\": " + (ok ? "true" : "false") + ", \"n\": " + std::to_string(items.size()) +
-                        ", \"route\": \"" + route + "\", \"products\": " + std::to_string(products) + ", \"items\": [";
+                        ", \"route\": \"" + route + "\", \"products\": " + std::to_string(products) + ", \"segmented_jobs\": " +
+                        std::to_string(segmented_jobs) + ", \"pipeline_jobs\": " + std::to_string(pipeline_jobs) + ", \"items\": [";
         for (size_t k = 0; k < items.size(); k++) d += (k ? ", " : "") + items[k].to_json();
         return d + "], \"seconds\": {\"parse\": " + num(parse_s) + ", \"membership\": " + num(membership_s) + ", \"fold\": " + num(fold_s) + ", \"pairings\": " +
                num(pairings_s) + ", \"total\": " + num(total_s) + "}}";
@@ -584,7 +588,9 @@ inline bool verify_batch(const Inputs &shared, const std::vector<BatchItem> &ite
     rep.items.assign(n, Report{});
     for (Report &r : rep.items) r.generator = rep.generator;
     rep.parse_s = since(t0);
+    const uint64_t seg0 = folder.segmented_jobs, pipe0 = folder.pipeline_jobs;
     auto finish = [&] {
+        rep.segmented_jobs = folder.segmented_jobs - seg0, rep.pipeline_jobs = folder.pipeline_jobs - pipe0;
         rep.ok = true;
         for (const Report &r : rep.items) rep.ok &= r.ok;
         rep.total_s = since(t_all);

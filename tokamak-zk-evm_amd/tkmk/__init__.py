@@ -97,7 +97,7 @@ SYMBOLS = [
     "tkmk_profile_reset", "tkmk_profile_get", "tkmk_diag_bench", "tkmk_diag_field_mul", "tkmk_diag_ffu", "tkmk_poly_find_degree",
     "tkmk_poly_place", "tkmk_poly_scale_coeffs", "tkmk_poly_mul_x_minus_one_evals", "tkmk_poly_mul_ones_x", "tkmk_poly_expr_eval", "tkmk_poly_expr_eval_views", "tkmk_poly_expr_eval_views_slab", "tkmk_poly_eval_x", "tkmk_poly_eval_y", "tkmk_poly_eval",
     "tkmk_poly_div_by_vanishing_opt", "tkmk_poly_div_by_ruffini", "tkmk_r1cs_eval_rows",
-    "tkmk_msm_multi_ex", "bls12_381_msm_convert_bases", "tkmk_r1cs_library_create", "tkmk_r1cs_library_destroy", "tkmk_r1cs_library_eval",
+    "tkmk_msm_multi_ex", "tkmk_msm_segmented", "tkmk_msm_segmented_status", "bls12_381_msm_convert_bases", "tkmk_r1cs_library_create", "tkmk_r1cs_library_destroy", "tkmk_r1cs_library_eval",
     "tkmk_r1cs_library_mix", "tkmk_fr_outer",
     "tkmk_witness_route", "tkmk_fr_scatter_table", "tkmk_msm_set_pipeline_streams", "tkmk_msm_get_pipeline_streams", "tkmk_host_malloc", "tkmk_host_free", "tkmk_stats_reset", "tkmk_stats_get",
     "bls12_381_ntt_domain_size", "bn254_ntt_domain_size", "tkmk_poly_lincomb", "tkmk_bintt_padded", "tkmk_diag_device_switch", "tkmk_diag_gather_probe",
@@ -605,16 +605,19 @@ def msm_convert_bases(bases, n=None, points_montgomery=False, out=None):
     return out
 
 
-def msm_job_ex_array(jobs):
+def msm_job_ex_array(jobs, count=True):
     """the tkmk_msm_job_ex array of a job list (see msm_multi_ex); "scalars" / "bases" may carry a byte offset into their buffer as
-    "scalar_offset" / "base_offset" (a rank's share of a view starts inside the table)"""
+    "scalar_offset" / "base_offset" (a rank's share of a view starts inside the table), "base_index" one as "index_offset";
+    count=False leaves STATS["msm_points"] alone (msm_segmented: its terms are counted by the library, apart from the MSM points)"""
     arr = (MsmJobEx * max(len(jobs), 1))()
     for k, j in enumerate(jobs):
         sv, bv, ix = j.get("scalar_view") or (0, 0), j.get("base_view") or (0, 0), j.get("base_index")
-        STATS["msm_points"] += int(j["n"])
+        if count:
+            STATS["msm_points"] += int(j["n"])
         tc, tf = j.get("table", (0, 0))                  # (c, factor) of a precomputed table (msm_precompute_bases over the whole table)
         arr[k] = MsmJobEx(_p(j["scalars"]).value + int(j.get("scalar_offset", 0)), _p(j["bases"]).value + int(j.get("base_offset", 0)), int(j["n"]),
-                          sv[0], sv[1], bv[0], bv[1], None if ix is None else _p(ix).value, int(j.get("table_len", 0)), int(tc), int(tf))
+                          sv[0], sv[1], bv[0], bv[1], None if ix is None else _p(ix).value + int(j.get("index_offset", 0)), int(j.get("table_len", 0)),
+                          int(tc), int(tf))
     return arr
 
 
@@ -631,6 +634,33 @@ def msm_multi_ex(jobs, bases_form=BASES_PLAIN, c=0, bitsize=0, stream=None):
     out = np.empty(144 * len(jobs), np.uint8)
     _check(lib().tkmk_msm_multi_ex(arr, len(jobs), ctypes.byref(cfg), int(bases_form), _p(out)), "tkmk_msm_multi_ex")
     return out
+
+
+MSM_SEGMENTED_MAX_SIZE = 4096               # TKMK_MSM_SEGMENTED_MAX_SIZE of include/tkmk.h: terms per job
+
+
+def msm_segmented(jobs, bases_form=BASES_PLAIN, bitsize=0, stream=None, results_on_device=False, scalars_montgomery=False, is_async=False):
+    """tkmk_msm_segmented: many ragged few-term MSMs (at most MSM_SEGMENTED_MAX_SIZE terms each) over views / index lists of resident
+    tables in two launches; jobs as msm_multi_ex (no table jobs).  Returns len(jobs) projective results, byte for byte msm_multi_ex's: on
+    the host, or with results_on_device a DeviceBuffer the finish kernel wrote.  is_async (device results only) returns without waiting
+    for the stream; msm_segmented_status(stream) then tells whether an index was out of range"""
+    cfg = lib().tkmk_msm_default_config()
+    cfg.are_scalars_on_device = cfg.are_points_on_device = True
+    cfg.bitsize, cfg.stream_handle = bitsize, stream
+    cfg.are_scalars_montgomery_form = scalars_montgomery
+    cfg.are_results_on_device, cfg.is_async = bool(results_on_device), bool(is_async)
+    if not jobs:
+        return DeviceBuffer(144) if results_on_device else np.empty(0, np.uint8)
+    arr = msm_job_ex_array(jobs, count=False)
+    out = DeviceBuffer(144 * len(jobs)) if results_on_device else np.empty(144 * len(jobs), np.uint8)
+    _check(lib().tkmk_msm_segmented(arr, len(jobs), ctypes.byref(cfg), int(bases_form), _p(out)), "tkmk_msm_segmented")
+    return out
+
+
+def msm_segmented_status(stream=None):
+    """tkmk_msm_segmented_status: waits for the stream; TkmkError (invalid argument) if an asynchronous msm_segmented call on it clamped an
+    out-of-range index since the last query"""
+    _check(lib().tkmk_msm_segmented_status(stream), "tkmk_msm_segmented_status")
 
 
 def poly_geometric_grid(rows, cols, c0, gx, gy, col0=0, col_step=1, out=None, stream=None):
@@ -730,7 +760,8 @@ def native_stats_reset():
 def native_stats():
     """work the library was asked to do since the last reset, counted inside the library (whichever host side called it)"""
     out = {}
-    for name in ("msm.points", "msm.calls", "msm.bucket_additions", "ntt.elements", "ntt.calls", "poly.elements"):
+    for name in ("msm.points", "msm.calls", "msm.bucket_additions", "ntt.elements", "ntt.calls", "poly.elements", "msm.segmented_jobs",
+                 "msm.segmented_terms"):
         v = ctypes.c_uint64()
         _check(lib().tkmk_stats_get(name.encode(), ctypes.byref(v)), "tkmk_stats_get")
         out[name] = v.value

@@ -103,8 +103,9 @@ def verify_batch(subcircuit_library_dir, crs_dir, items, root_generator=0, route
     """tkmk_verify_batch_files: items = [(synthesizer_dir, preprocess_dir, proof_dir)], proofs of ONE circuit against ONE reference string
     -> (ok_each: list of bool, report).  ok_each[k] is what verify_files says for item k alone; an all-honest batch costs one product of
     ten pairings (report["products"] == 1), false items are isolated by bisection with fresh weights.  route: "host" (no device call) or
-    "device" (one tkmk_g1_check, one tkmk_msm_multi_ex per fold; TKMK_ERR_NO_DEVICE without one).  report = {"generator", "ok", "n",
-    "route", "products", "items": [a verify_files report per item], "seconds"}.  service.ProverError for an empty batch (code 11) and for
+    "device" (one tkmk_g1_check, per fold one tkmk_msm_segmented call and, for slot jobs too long for it, one tkmk_msm_multi_ex call;
+    TKMK_ERR_NO_DEVICE without one).  report = {"generator", "ok", "n", "route", "products", "segmented_jobs", "pipeline_jobs" (the device
+    route's slot jobs by MSM entry, over all folds), "items": [a verify_files report per item], "seconds"}.  service.ProverError for an empty batch (code 11) and for
     unreadable input (the message names the item and the file)."""
     l = _lib(testing)
     each, ok, doc = (ctypes.c_uint8 * max(len(items), 1))(), ctypes.c_int(-1), ctypes.c_void_p()

@@ -74,7 +74,10 @@ def main():
                 t = time.perf_counter()
                 rep = fn()
                 runs.append((time.perf_counter() - t, rep))
+            walls.append(sorted(round(r[0], 6) for r in runs))
             return min(runs, key=lambda r: r[0])
+
+        walls = []                                                                      # every repeat's wall time of the last best() calls
 
         for n in sizes:
             row = {}
@@ -91,7 +94,9 @@ def main():
                     wall, (each, rep) = best(lambda: verify.verify_batch_with(ctx, items, route=route))
                     assert each == want and rep["route"] == route, (n, route, name)
                     row["%s_%s" % (route, name)] = {"wall_s": round(wall, 6), "per_proof_s": round(wall / n, 6), "products": rep["products"],
-                                                    "seconds": rep["seconds"], "speedup_vs_single": round(row["single"]["wall_s"] / wall, 2)}
+                                                    "seconds": rep["seconds"], "speedup_vs_single": round(row["single"]["wall_s"] / wall, 2),
+                                                    "repeats_wall_s": walls[-1],        # sorted: the spread between the best two is the run's noise
+                                                    "segmented_jobs": rep.get("segmented_jobs", 0), "pipeline_jobs": rep.get("pipeline_jobs", 0)}
             result["sizes"][str(n)] = row
             print("N = %d: %s" % (n, json.dumps(row)), file=sys.stderr, flush=True)
     os.makedirs(os.path.dirname(out_path), exist_ok=True)
