@@ -684,6 +684,26 @@ tkmk_error tkmk_witness_route(const tkmk_fr *vars_dev, const uint64_t *var_offse
  * TKMK_ERR_INVALID_ARGUMENT after the valid entries were written (the reference indexes a Vec and panics). */
 tkmk_error tkmk_fr_scatter_table(const tkmk_fr *table_dev, uint64_t table_len, const uint32_t *src_idx_dev, const uint32_t *dst_idx_dev,
                                  uint64_t n, tkmk_fr *out_dev, uint64_t out_len, tkmk_stream stream);
+/* The witness check (csrc/witcheck.hip; host/tkmk_witness_check.hpp) — the reference's testing-mode diagnostics (prove/src/lib.rs:916-1017,
+ * 1472-1518) as two streaming passes over grids Prover::init has already built.  Device pointers, plain Fr; both return after the kernel.
+ *
+ * _r1cs: for every cell (row, col), row < n_rows, col < n_cols, of three grids with element (row, col) at row * stride + col (the layout
+ * tkmk_r1cs_library_eval writes) decides whether u . v = w in Fr.  bad_count_dev[col] = the number of failing rows of that column,
+ * first_bad_row_dev[col] = the smallest of them, 0xFFFFFFFF when there is none: n_cols uint32 each, fully written.  *total_bad_out (host) =
+ * the sum of the counts.  The padding columns n_cols <= col < stride are neither read nor written.  A count and a minimum: the outputs do
+ * not depend on scheduling.  TKMK_ERR_INVALID_ARGUMENT for n_cols > stride and n_rows = 0xFFFFFFFF.
+ *
+ * _copy: for every entry e < n_entries compares b[dst_idx[e]] with b[src_x[e] * stride + src_y[e]] over a rows x cols grid of the same
+ * layout (dst_idx = row * stride + col).  *bad_entries_out = the number of entries whose two cells differ, *first_bad_entry_out = the
+ * smallest such e, UINT64_MAX when there is none (both host).  An entry that points outside rows x cols is never dereferenced and takes
+ * no part in the two results; the call then returns TKMK_ERR_INVALID_ARGUMENT after the valid entries were judged — the contract of
+ * tkmk_fr_scatter_table.  n_entries = 0 is success with zero bad entries. */
+tkmk_error tkmk_witness_check_r1cs(const tkmk_fr *u_dev, const tkmk_fr *v_dev, const tkmk_fr *w_dev, uint32_t n_rows, uint32_t n_cols,
+                                   uint32_t stride, uint32_t *bad_count_dev, uint32_t *first_bad_row_dev, uint64_t *total_bad_out,
+                                   tkmk_stream stream);
+tkmk_error tkmk_witness_check_copy(const tkmk_fr *b_dev, uint32_t rows, uint32_t cols, uint32_t stride, const uint32_t *dst_idx_dev,
+                                   const uint32_t *src_x_dev, const uint32_t *src_y_dev, uint64_t n_entries, uint64_t *bad_entries_out,
+                                   uint64_t *first_bad_entry_out, tkmk_stream stream);
 /* pinned host memory for staging (HostSlice buffers the reference uploads from are pageable; pinned staging reaches link rate) */
 tkmk_error tkmk_host_malloc(void **ptr, size_t bytes);
 tkmk_error tkmk_host_free(void *ptr);

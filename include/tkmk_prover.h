@@ -217,6 +217,35 @@ tkmk_error tkmk_crs_audit_files(const char *subcircuit_library_dir, const char *
  * delta_small, alpha_chain, singles (an empty table is vacuously ok with 0 points), "table_seconds": {"library", "grids", "msm", "pairings"}. */
 tkmk_error tkmk_crs_audit_circuit_files(const char *subcircuit_library_dir, const char *crs_dir, int *ok, char **report_json_out);
 
+/* ---- The witness check (host/tkmk_witness_check.hpp; needs a device and NO reference string) ----
+ * Reads the library (<lib>/setupParams.json, subcircuitInfo.json, r1cs/) and the three per-proof documents of synthesizer_dir, puts the
+ * witness on the device exactly as Prover::init does (the same code) and decides three sections, always all three: *ok = 1 iff
+ *   arithmetic   every placement's variables satisfy its subcircuit's R1CS: u . v = w in every cell of the n x s_max evaluation grids
+ *                (tkmk_witness_check_r1cs);
+ *   copy         every entry {row, col, X, Y} of the effective permutation (the last writer of a cell wins, as in init) ties two equal
+ *                interface values, b[row][col] = b[X][Y] (tkmk_witness_check_copy), and that map, extended by the identity on the
+ *                cells no entry writes, is a bijection of the m_I x s_max cells;
+ *   public       every public wire of placements 0..3 (the outputs of bufferPubOut, the inputs of bufferPubIn / bufferBlockIn /
+ *                bufferEVMIn) equals the value of instance.json (a_pub_user ++ a_pub_block ++ a_pub_function) at its flattenMap index.
+ * The verifier defines "wrong": *ok is what tkmk_prover_verify answers for the proof the prover makes from the same documents.
+ * TKMK_SUCCESS after either verdict; an unreadable or malformed document is an error whose message names the file, and so is a machine
+ * without a device (TKMK_ERR_NO_DEVICE).  report_json_out (optional, tkmk_prover_free_string): {"ok", "reason" (the first finding of
+ * the first failing section, "" when ok), "arithmetic": {"ok", "placements", "bad_placements", "bad_cells", "first": [{"placement",
+ * "subcircuitId", "name", "first_row", "bad_rows", "u", "v", "w"}]}, "copy": {"ok", "entries", "bijection", "hit_twice" ({"row", "col"},
+ * present when not a bijection), "bad_entries", "first": [{"entry", "row", "col", "X", "Y", "value", "source"}]}, "public": {"ok", "wires",
+ * "bad", "first": [{"index", "placement", "wire", "value", "instance"}]}, "seconds": {"parse", "upload", "build", "check", "total"}} — at
+ * most 8 findings per section, field values as 0x + 64 hex digits.  Not covered: sharded contexts, BN254, WHICH variable of a failing row
+ * is wrong. */
+tkmk_error tkmk_witness_check_files(const char *subcircuit_library_dir, const char *synthesizer_dir, int *ok, char **report_json_out);
+/* The same against a resident context's library (nothing is read from subcircuit_library_dir again): own device buffers, a turn on the
+ * default stream like a proof, and nothing a later tkmk_prover_prove reads is changed.  On a context from tkmk_prover_open_sharded it
+ * returns TKMK_ERR_INVALID_ARGUMENT: the copy section compares cells of different columns, which live on different ranks.
+ * TKMK_PROVER_CHECK_WITNESS=1 in the environment makes tkmk_prover_prove[_ex] (and bin/prove) run the three sections inside init, on the
+ * grids it has just built, before the binding commitments are issued: a witness that fails is refused with TKMK_ERR_INVALID_ARGUMENT,
+ * tkmk_prover_last_error() carries the report's "reason", no proof.json is written and the context stays usable.  Unset or 0: nothing is
+ * launched and nothing is downloaded.  A sharded context does not read the variable. */
+tkmk_error tkmk_prover_check_witness(tkmk_prover *p, const char *synthesizer_dir, int *ok, char **report_json_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -207,6 +207,36 @@ TKP_API tkmk_error tkmk_crs_audit_circuit_files(const char *subcircuit_library_d
     return crs_audit_entry("tkmk_crs_audit_circuit_files", subcircuit_library_dir, crs_dir, true, ok, report_json_out);
 }
 
+// the witness check (host/tkmk_witness_check.hpp; ProverContext::check_witness): device work on the default stream, like a proof
+TKP_API tkmk_error tkmk_witness_check_files(const char *subcircuit_library_dir, const char *synthesizer_dir, int *ok, char **report_json_out) {
+    if (!subcircuit_library_dir || !synthesizer_dir || !ok) return TKMK_ERR_INVALID_POINTER;
+    *ok = 0;
+    if (report_json_out) *report_json_out = nullptr;
+    return guarded([&] {
+        int ndev = 0;
+        if (tkmk_device_count(&ndev) != TKMK_SUCCESS || ndev < 1) throw Error(TKMK_ERR_NO_DEVICE, "tkmk_witness_check_files: no HIP device (the MI355X backend has no CPU fallback)");
+        DefaultStreamTurn turn(false);
+        std::unique_ptr<ProverContext> ctx = ProverContext::open_circuit(subcircuit_library_dir);   // no reference string
+        witness_check::Report rep;
+        const bool verdict = ctx->check_witness(synthesizer_dir, rep);
+        if (report_json_out) *report_json_out = dup_string(rep.to_json());
+        *ok = verdict ? 1 : 0;
+    });
+}
+TKP_API tkmk_error tkmk_prover_check_witness(tkmk_prover *p, const char *synthesizer_dir, int *ok, char **report_json_out) {
+    if (!p || !synthesizer_dir || !ok) return TKMK_ERR_INVALID_POINTER;
+    *ok = 0;
+    if (report_json_out) *report_json_out = nullptr;
+    return guarded([&] {
+        if (p->ctx->link) throw Error("tkmk_prover_check_witness: not available on a sharded context (the copy section crosses columns: it would need a collective)");
+        DefaultStreamTurn turn(false);
+        witness_check::Report rep;
+        const bool verdict = p->ctx->check_witness(synthesizer_dir, rep);
+        if (report_json_out) *report_json_out = dup_string(rep.to_json());
+        *ok = verdict ? 1 : 0;
+    });
+}
+
 TKP_API tkmk_error tkmk_prover_verify(tkmk_prover *p, const char *synthesizer_dir, const char *preprocess_dir, const char *proof_dir, int *ok,
                                       char **report_json_out) {
     if (!p || !synthesizer_dir || !preprocess_dir || !proof_dir || !ok) return TKMK_ERR_INVALID_POINTER;

@@ -1,6 +1,6 @@
 // tkmk_circuit.hpp — what a circuit looks like: the two static documents of a subcircuit library directory and its constraint files, with
-// one reader and one shape check for the setup, `preprocess`, the CRS audit and the verifier (ProverContext::open and Prover::init still
-// inline theirs).  Device-free (no call into libtkmk_hip.so), so the host-only verifier can include it.
+// one reader and one shape check for the setup, `preprocess`, the CRS audit, the verifier, the resident prover (ProverContext::open_circuit)
+// and through it the witness check (Prover::init still inlines its own).  Device-free (no call into libtkmk_hip.so), so the host-only verifier can include it.
 //   SetupParams, validate_setup_shape                    <lib>/setupParams.json; setup_shape / validate_setup_shape (libs/src/utils/mod.rs:21-46);
 //                                                        the shape of the CRS grid xy_powers that follows from it
 //   SubcircuitInfo, SubcircuitLibrary                    <lib>/subcircuitInfo.json in file order (libs/src/iotools/mod.rs:458-469) and per

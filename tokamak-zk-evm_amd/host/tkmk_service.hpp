@@ -20,6 +20,7 @@
 #include "tkmk_fastparse.hpp"
 #include "tkmk_inputs.hpp"
 #include "tkmk_prover.hpp"
+#include "tkmk_witness_check.hpp"
 
 namespace tkmk {
 
@@ -123,59 +124,34 @@ class ProverContext {
                            jp.at("s_max").as_size()};
     }
 
-    // circuit-static state: subcircuit library from <lib_dir>, reference string from <crs_dir> (combined_sigma.rkyv, or the flat
-    // combined_sigma.tkcrs payload when only that is present)
-    // link set: load_sigma returns this rank's columns of xy_powers; everything derived from them (table expansion, the Lagrange-basis
-    // tables and their prefix sums) is made from those columns, 1 / G of the work per rank
-    // load_sigma hands its third argument to ProverSigma::from_payload: the hook that identifies the root of unity the CRS was made under
-    // (identify_crs_root, host/tkmk_prover.hpp) while the uploaded table is still whole and plain.  Nothing that depends on omega — the NTT
-    // domain, the identity part of s0 / s1, the Lagrange tables — exists before it has run.
-    static std::unique_ptr<ProverContext> open(const std::string &lib_dir, const std::string &crs_dir,
-                                               const std::function<std::unique_ptr<ProverSigma>(const SetupParams &, std::string &, const CrsGridHook &)> &load_sigma,
-                                               const ShardLink &link = ShardLink{}) {
+    // The part of open that needs no reference string: the shape, the subcircuit infos, the constraint library as device CSR and the static
+    // wire lists, all from the one circuit reader (host/tkmk_circuit.hpp).  open() goes on from here; the stand-alone witness check
+    // (tkmk_witness_check_files) stops here: its context has no sigma, no NTT domain and no Lagrange tables, and only check_witness runs on it.
+    static std::unique_ptr<ProverContext> open_circuit(const std::string &lib_dir, const ShardLink &link = ShardLink{}) {
         std::unique_ptr<ProverContext> c(new ProverContext());
         c->link = link;
-        ShardSpan span(c->link);
         c->lib_dir = lib_dir;
         c->threads = host_threads();
-        c->sp = read_setup_params(lib_dir);
+        c->sp = SetupParams::read(lib_dir);
         const SetupParams &sp = c->sp;
-        if (sp.l_D < sp.l) throw Error("Invalid setup params: l_D must be >= l.");   // setup_shape / validate_setup_shape (libs/src/utils/mod.rs:21-46)
-        c->m_i = sp.l_D - sp.l;
-        if (!is_pow2(sp.n)) throw Error("n is not a power of two.");
-        if (!is_pow2(sp.s_max)) throw Error("s_max is not a power of two.");
-        if (!is_pow2(c->m_i)) throw Error("m_I is not a power of two.");
+        validate_setup_shape(sp);   // setup_shape / validate_setup_shape (libs/src/utils/mod.rs:21-46)
+        c->m_i = sp.m_i();
         if (c->link && c->link.shard.world > 1) {
             const size_t G = c->link.shard.world;
             if (!is_pow2(G)) throw Error("sharded prover: the number of ranks must be a power of two");
             if (G > sp.s_max || G > std::min(sp.n, c->m_i)) throw Error("sharded prover: more ranks than the circuit has columns (s_max) or rows (n, m_I)");
         }
-        {
-            const json::Value jinfo = json::read_file(lib_dir + "/subcircuitInfo.json");
-            for (const json::Value &e : jinfo.items()) {
-                SubcircuitInfo si;
-                si.id = e.at("id").as_size();
-                si.name = e.at("name").as_string();
-                si.Nwires = e.at("Nwires").as_size();
-                si.Out_idx = {e.at("Out_idx").items().at(0).as_size(), e.at("Out_idx").items().at(1).as_size()};
-                si.In_idx = {e.at("In_idx").items().at(0).as_size(), e.at("In_idx").items().at(1).as_size()};
-                for (const json::Value &g : e.at("flattenMap").items()) si.flattenMap.push_back(g.as_size());
-                c->infos.push_back(std::move(si));
-                c->n_consts.push_back(e.at("Nconsts").as_size());
-            }
-        }
+        SubcircuitLibrary library = SubcircuitLibrary::read(lib_dir, sp);
+        c->infos = std::move(library.infos), c->n_consts = std::move(library.n_consts);
         // constraint library -> device CSR, and the static wire lists
         const size_t K = c->infos.size();
-        std::vector<SubcircuitR1CS> r1cs(K);
+        const std::vector<SubcircuitR1CS> &r1cs = library.r1cs;
         std::vector<uint32_t> n_rows(K), n_wires(K);
         std::vector<const uint32_t *> rp(3 * K), wr(3 * K);
         std::vector<const tkmk_fr *> cf(3 * K);
         std::vector<std::vector<std::pair<uint32_t, uint32_t>>> iface(K), prv(K), pub(K);
         for (size_t k = 0; k < K; k++) {
             const SubcircuitInfo &info = c->infos[k];
-            if (info.flattenMap.size() != info.Nwires) throw Error("subcircuitInfo.json: flattenMap length differs from Nwires for subcircuit " + std::to_string(info.id));
-            R1csBinary b = R1csBinary::read(lib_dir + "/r1cs/subcircuit" + std::to_string(info.id) + ".r1cs");
-            r1cs[k] = SubcircuitR1CS::from_r1cs_sparse_only(b, sp, info, c->n_consts[k]);
             n_rows[k] = r1cs[k].n_constraints, n_wires[k] = r1cs[k].n_wires;
             for (int m = 0; m < 3; m++) rp[3 * k + m] = r1cs[k].row_ptr[m].data(), wr[3 * k + m] = r1cs[k].wire[m].data(), cf[3 * k + m] = r1cs[k].coeff[m].data();
             for (size_t j = 0; j < info.Nwires; j++) {
@@ -197,6 +173,22 @@ class ProverContext {
         check(tkmk_r1cs_library_create((uint32_t)K, n_rows.data(), n_wires.data(), rp.data(), wr.data(), cf.data(), &c->lib_), "tkmk_r1cs_library_create");
         c->n_wires_ = n_wires;
         c->iface_ = make_lists(iface), c->prv_ = make_lists(prv), c->pub_ = make_lists(pub);
+        return c;
+    }
+
+    // circuit-static state: subcircuit library from <lib_dir>, reference string from <crs_dir> (combined_sigma.rkyv, or the flat
+    // combined_sigma.tkcrs payload when only that is present)
+    // link set: load_sigma returns this rank's columns of xy_powers; everything derived from them (table expansion, the Lagrange-basis
+    // tables and their prefix sums) is made from those columns, 1 / G of the work per rank
+    // load_sigma hands its third argument to ProverSigma::from_payload: the hook that identifies the root of unity the CRS was made under
+    // (identify_crs_root, host/tkmk_prover.hpp) while the uploaded table is still whole and plain.  Nothing that depends on omega — the NTT
+    // domain, the identity part of s0 / s1, the Lagrange tables — exists before it has run.
+    static std::unique_ptr<ProverContext> open(const std::string &lib_dir, const std::string &crs_dir,
+                                               const std::function<std::unique_ptr<ProverSigma>(const SetupParams &, std::string &, const CrsGridHook &)> &load_sigma,
+                                               const ShardLink &link = ShardLink{}) {
+        std::unique_ptr<ProverContext> c = open_circuit(lib_dir, link);
+        ShardSpan span(c->link);
+        const SetupParams &sp = c->sp;
 
         host_trace("open: loading the CRS");
         bool identified = false;
@@ -356,132 +348,91 @@ class ProverContext {
         return c;
     }
 
-    // Prover::init (prove/src/lib.rs:675-1206) from the synthesizer's directory
-    // pending (optional): when given and this context is not sharded, the binding batch is left running and *pending holds it (it borrows
-    // the returned prover's a_free_X); finish_binding() completes the returned Binding later.  Otherwise the Binding is complete on return.
-    std::pair<std::unique_ptr<Prover>, Binding> init(const std::string &synth_dir, const Mixer &mixer, ProveTiming &tm, CommitBatch::Pending *pending = nullptr) {
-        using namespace prover_detail;
-        const double t0 = Prover::now();
-        const size_t n = sp.n, s_max = sp.s_max, K = infos.size();
-        host_trace("init: begin");
-
-        // ---- the three per-proof documents.  permutation.json first (every host thread, ~1 ms); then the (fourteen times larger) witness
-        // document is read on a helper — with every host thread again — while this one, mostly waiting on the device, builds the
-        // permutation's two polynomials; the two meet before the witness upload.
-        // Sharded: every rank reads the whole document's structure and every placement's kind, but converts (and thereby checks) only the
-        // values of its own placements — so an input error may show on one rank only.  The ranks therefore AGREE on the outcome of this
-        // phase before any of them goes on: a malformed document is then the same error on every rank, at the same point.
-        const Shard sh = link ? link.shard : Shard{};
+    // The witness onto the device: the parse of the three per-proof documents, one upload, tkmk_r1cs_library_eval, the interface route into
+    // b and the permutation's arrays — the part of Prover::init (prove/src/lib.rs:675-1206) that init and the witness check
+    // (check_witness, host/tkmk_witness_check.hpp) share.  One object per proof; its steps run once each, in the order they are declared
+    // in, and init interleaves its own work (s0 / s1, the polynomials) between them exactly where it always issued it.
+    //
+    // permutation.json first (every host thread, ~1 ms); then the (fourteen times larger) witness document is read on a helper — with every
+    // host thread again — while the caller, mostly waiting on the device, goes on; the two meet in join(), before the witness upload.
+    // Sharded: every rank reads the whole document's structure and every placement's kind, but converts (and thereby checks) only the
+    // values of its own placements — so an input error may show on one rank only.  The ranks therefore AGREE on the outcome of this
+    // phase before any of them goes on: a malformed document is then the same error on every rank, at the same point.
+    class WitnessLoader {
+      public:
+        ProverContext &c;
+        const Shard sh;
+        const size_t lc;                                               // this rank's columns of s_max
         WitnessLayout W;
-        std::vector<ScalarField> a_pub_user, a_pub_block;
-        std::unique_ptr<Prover> p(new Prover());
-        p->sp = sp, p->m_i = m_i, p->sigma = sigma.get(), p->mixer = mixer, p->lagrange = lagrange_;
-        if (!link) {
-            if (!commit_stream_) check(tkmk_stream_create(&commit_stream_), "stream_create");
-            p->commit_stream = commit_stream_;
-        }
-        MappedFile perm_file(synth_dir + "/permutation.json");
-        PermutationColumns perm = parse_permutation_fast(perm_file.data(), perm_file.size(), threads);
-        host_trace("init: permutation.json parsed (%zu entries)", perm.size());
-        // (the helper signals as soon as the values are staged; unmapping the 88 MB document — milliseconds of page-table work — happens
-        // after the signal, beside the upload)
-        std::promise<void> witness_staged;
-        std::future<void> witness_read = witness_staged.get_future();
-        struct Joined {
-            std::thread t;
-            ~Joined() { if (t.joinable()) t.join(); }
-        } witness_reader{std::thread([&] {
-            std::unique_ptr<MappedFile> pv_file;
-            try {
-                pv_file.reset(new MappedFile(synth_dir + "/placementVariables.json"));
-                W = parse_placement_variables_fast(pv_file->data(), pv_file->size(), n_wires_, [&](uint64_t total) { return staging(total); }, threads, sh.world, sh.rank);
-                host_trace("init: placementVariables.json parsed (%zu placements, %llu values kept)", W.id.size(), (unsigned long long)W.total);
-                if (W.id.size() > s_max) throw Error("placement_variables length exceeds s_max.");
-                const json::Value jinst = json::read_file(synth_dir + "/instance.json");
-                a_pub_user = hex_list(jinst.at("a_pub_user"));
-                a_pub_block = hex_list(jinst.at("a_pub_block"));
-                witness_staged.set_value();
-            } catch (...) {
-                witness_staged.set_exception(std::current_exception());
-            }
-        })};
-        DeviceVec<uint32_t> d_dst, d_x, d_y;   // alive until the kernels reading them have run (synchronised before init returns)
-        {
-            // Permutation::to_poly's redirects: distinct destinations (the reference's serial loop lets the last entry win)
-            std::vector<uint32_t> dst, srcx, srcy;
-            const size_t cells = m_i * s_max;
-            std::vector<uint64_t> bitmap((cells + 63) / 64, 0);
-            bool dup = false;
-            dst.reserve(perm.size());
-            for (size_t e = 0; e < perm.size(); e++) {
-                if (perm.row[e] >= m_i || perm.col[e] >= s_max || perm.X[e] >= m_i || perm.Y[e] >= s_max) throw Error("permutation entry out of range");
-                uint32_t d = perm.row[e] * (uint32_t)s_max + perm.col[e];
-                if (bitmap[d >> 6] >> (d & 63) & 1) dup = true;
-                bitmap[d >> 6] |= 1ull << (d & 63);
-                dst.push_back(d);
-            }
-            srcx = perm.X, srcy = perm.Y;
-            if (dup) {   // keep the last writer of every cell
-                std::fill(bitmap.begin(), bitmap.end(), 0);
-                std::vector<uint32_t> d2, x2, y2;
-                for (size_t e = perm.size(); e-- > 0;) {
-                    uint32_t d = dst[e];
-                    if (bitmap[d >> 6] >> (d & 63) & 1) continue;
-                    bitmap[d >> 6] |= 1ull << (d & 63);
-                    d2.push_back(d), x2.push_back(srcx[e]), y2.push_back(srcy[e]);
-                }
-                dst.swap(d2), srcx.swap(x2), srcy.swap(y2);
+        std::vector<ScalarField> a_pub_user, a_pub_block, a_pub_function;
+        witness_check::EffectivePermutation perm;                      // the redirects of every rank's cells, global indices
+        std::vector<uint32_t> local_dst, local_x, local_y;             // sharded: those of this rank's columns, local destinations
+        DeviceVec<uint32_t> d_dst, d_x, d_y;                           // alive until the kernels reading them have run
+        size_t P = 0, PL = 0;                                          // placements of the proof, and of this rank
+        std::vector<uint32_t> kind_first, slots, gslots, ids_local;
+        std::vector<uint64_t> offs, offs_local;
+        DeviceVec<ScalarField> d_vars;
+        DeviceVec<uint32_t> d_id, d_slots, d_gslots;
+        DeviceVec<uint64_t> d_off, d_offs;
+        DeviceVec<ScalarField> u, v, w, b_ev, mid_sc, prv_sc, pub_sc;
+        DeviceVec<uint32_t> mid_ix, prv_ix, pub_ix;
+        uint64_t n_mid = 0, n_prv = 0, n_pub = 0;
+
+        const std::vector<uint32_t> &dst() const { return sh.world > 1 ? local_dst : perm.dst; }
+        const std::vector<uint32_t> &srcx() const { return sh.world > 1 ? local_x : perm.x; }
+        const std::vector<uint32_t> &srcy() const { return sh.world > 1 ? local_y : perm.y; }
+
+        // with_function: a_pub_function of instance.json too (the public section of the witness check reads it; a proof does not)
+        WitnessLoader(ProverContext &ctx, const std::string &synth_dir, bool with_function) : c(ctx), sh(ctx.link ? ctx.link.shard : Shard{}), lc(sh.cols_of(ctx.sp.s_max)) {
+            const size_t s_max = c.sp.s_max;
+            {
+                MappedFile perm_file(synth_dir + "/permutation.json");
+                PermutationColumns cols = parse_permutation_fast(perm_file.data(), perm_file.size(), c.threads);
+                host_trace("init: permutation.json parsed (%zu entries)", cols.size());
+                start_reader(synth_dir, with_function);
+                // Permutation::to_poly's redirects: distinct destinations (the reference's serial loop lets the last entry win)
+                perm = witness_check::effective_permutation(cols, c.m_i, s_max);
             }
             // Permutation::to_poly (libs/src/iotools/mod.rs:419-455).  Sharded: this rank redirects the cells of its own columns
             // (col = rank mod G; local cell row * lc + col / G); the sources X, Y stay global indices into the two power tables
-            const size_t lc = sh.cols_of(s_max);
-            if (sh.world > 1) {
-                std::vector<uint32_t> d2, x2, y2;
-                for (size_t e = 0; e < dst.size(); e++) {
-                    const uint32_t row = dst[e] / (uint32_t)s_max, col = dst[e] % (uint32_t)s_max;
+            if (sh.world > 1)
+                for (size_t e = 0; e < perm.dst.size(); e++) {
+                    const uint32_t row = perm.dst[e] / (uint32_t)s_max, col = perm.dst[e] % (uint32_t)s_max;
                     if (col % sh.world != sh.rank) continue;
-                    d2.push_back(row * (uint32_t)lc + col / sh.world), x2.push_back(srcx[e]), y2.push_back(srcy[e]);
+                    local_dst.push_back(row * (uint32_t)lc + col / sh.world), local_x.push_back(perm.x[e]), local_y.push_back(perm.y[e]);
                 }
-                dst.swap(d2), srcx.swap(x2), srcy.swap(y2);
+        }
+        void upload_permutation() {
+            if (dst().empty()) return;
+            d_dst = DeviceVec<uint32_t>::from_host(dst()), d_x = DeviceVec<uint32_t>::from_host(srcx()), d_y = DeviceVec<uint32_t>::from_host(srcy());
+        }
+        // the witness documents are staged; placements grouped by kind: slot list, variable offsets, position of each kind's run.  Sharded: a
+        // placement is a column of u, v, w, b — this rank takes the placements q = rank mod G; `slots` are their local columns q / G,
+        // `gslots` the global ones (the binding tables are indexed by the global slot)
+        void join() {
+            const size_t K = c.infos.size();
+            std::string input_error;
+            try {
+                read_.get();
+                host_trace("init: witness documents joined");
+            } catch (const std::exception &e) {
+                if (sh.world == 1) throw;
+                input_error = e.what();
+                if (input_error.empty()) input_error = "input error";
             }
-            DeviceVec<ScalarField> e0 = s0_identity_.clone(), e1 = s1_identity_.clone();
-            if (!dst.empty()) {
-                d_dst = DeviceVec<uint32_t>::from_host(dst), d_x = DeviceVec<uint32_t>::from_host(srcx), d_y = DeviceVec<uint32_t>::from_host(srcy);
-                check(tkmk_fr_scatter_table(xp_.ptr(), xp_.len(), d_x.ptr(), d_dst.ptr(), dst.size(), e0.ptr(), e0.len(), nullptr), "tkmk_fr_scatter_table");
-                check(tkmk_fr_scatter_table(yp_.ptr(), yp_.len(), d_y.ptr(), d_dst.ptr(), dst.size(), e1.ptr(), e1.len(), nullptr), "tkmk_fr_scatter_table");
+            if (sh.world > 1) {
+                const tkmk_error verdict = c.link.agree(c.link.comm, input_error.empty() ? TKMK_SUCCESS : TKMK_ERR_INVALID_ARGUMENT);
+                if (!input_error.empty()) throw Error(input_error);
+                if (verdict != TKMK_SUCCESS) throw Error("another rank of the sharded prover could not read its share of the synthesizer's documents");
             }
-            p->s0XY = Poly::from_rou_evals_cols(e0, m_i, s_max), p->s1XY = Poly::from_rou_evals_cols(e1, m_i, s_max);
-            p->s0_ev = std::move(e0), p->s1_ev = std::move(e1);   // prove1 forms f and g on the grid from these
-            p->s0_identity = &s0_identity_, p->s1_identity = &s1_identity_;
-        }
-        host_trace("init: s0 / s1 issued");
-        std::string input_error;
-        try {
-            witness_read.get();
-            host_trace("init: witness documents joined");
-        } catch (const std::exception &e) {
-            if (sh.world == 1) throw;
-            input_error = e.what();
-            if (input_error.empty()) input_error = "input error";
-        }
-        if (sh.world > 1) {
-            const tkmk_error verdict = link.agree(link.comm, input_error.empty() ? TKMK_SUCCESS : TKMK_ERR_INVALID_ARGUMENT);
-            if (!input_error.empty()) throw Error(input_error);
-            if (verdict != TKMK_SUCCESS) throw Error("another rank of the sharded prover could not read its share of the synthesizer's documents");
-        }
-        const size_t P = W.id.size();
-        // placements grouped by kind: slot list, variable offsets, position of each kind's run.  Sharded: a placement is a column of
-        // u, v, w, b — this rank takes the placements q = rank mod G; `slots` are their local columns q / G, `gslots` the global ones
-        // (the binding tables are indexed by the global slot)
-        const size_t lc = sh.cols_of(s_max);
-        std::vector<uint32_t> mine_q;
-        for (size_t q = sh.rank; q < P; q += sh.world) mine_q.push_back((uint32_t)q);
-        const size_t PL = mine_q.size();
-        std::vector<uint32_t> kind_first(K + 1, 0), slots(PL ? PL : 1), gslots(PL ? PL : 1), ids_local(PL ? PL : 1);
-        std::vector<uint64_t> offs(PL ? PL : 1), offs_local(PL ? PL : 1);
-        for (size_t k = 0; k < PL; k++) kind_first[W.id[mine_q[k]] + 1]++, ids_local[k] = W.id[mine_q[k]], offs_local[k] = W.off[mine_q[k]];
-        for (size_t k = 0; k < K; k++) kind_first[k + 1] += kind_first[k];
-        {
+            P = W.id.size();
+            std::vector<uint32_t> mine_q;
+            for (size_t q = sh.rank; q < P; q += sh.world) mine_q.push_back((uint32_t)q);
+            PL = mine_q.size();
+            kind_first.assign(K + 1, 0), slots.assign(PL ? PL : 1, 0), gslots.assign(PL ? PL : 1, 0), ids_local.assign(PL ? PL : 1, 0);
+            offs.assign(PL ? PL : 1, 0), offs_local.assign(PL ? PL : 1, 0);
+            for (size_t k = 0; k < PL; k++) kind_first[W.id[mine_q[k]] + 1]++, ids_local[k] = W.id[mine_q[k]], offs_local[k] = W.off[mine_q[k]];
+            for (size_t k = 0; k < K; k++) kind_first[k + 1] += kind_first[k];
             std::vector<uint32_t> cur(kind_first.begin(), kind_first.end() - 1);
             for (size_t k = 0; k < PL; k++) {
                 const uint32_t q = mine_q[k];
@@ -489,79 +440,212 @@ class ProverContext {
                 slots[at] = (uint32_t)k, gslots[at] = q, offs[at] = W.off[q];
             }
         }
+        // one upload of the witness and of the small index arrays
+        void upload() {
+            d_vars = DeviceVec<ScalarField>((size_t)W.total + 1);
+            if (W.total) check(tkmk_memcpy_h2d(d_vars.ptr(), c.pinned_, (size_t)W.total * sizeof(ScalarField)), "witness upload");
+            d_id = DeviceVec<uint32_t>::from_host(ids_local);
+            d_off = DeviceVec<uint64_t>::from_host(offs_local);
+            d_slots = DeviceVec<uint32_t>::from_host(slots), d_gslots = DeviceVec<uint32_t>::from_host(gslots);
+            d_offs = DeviceVec<uint64_t>::from_host(offs);
+        }
+        // read_R1CS_gen_uvwXY (libs/src/iotools/mod.rs:1287-1420): one column per placement — this rank's placements, its columns
+        void eval_uvw() {
+            const size_t n = c.sp.n;
+            u = DeviceVec<ScalarField>(n * lc), v = DeviceVec<ScalarField>(n * lc), w = DeviceVec<ScalarField>(n * lc);
+            check(tkmk_r1cs_library_eval(c.lib_, d_vars.ptr(), d_id.ptr(), d_off.ptr(), (uint32_t)PL, (uint32_t)n, (uint32_t)lc, u.ptr(), v.ptr(), w.ptr(), nullptr),
+                  "tkmk_r1cs_library_eval");
+        }
+        // gen_bXY and — binding_lists — the (scalar, CRS row) lists of O_mid / O_prv / O_pub_free, kind by kind
+        void route(bool binding_lists) {
+            const size_t K = c.infos.size(), s_max = c.sp.s_max, m_i = c.m_i;
+            const WireLists &iface_ = c.iface_, &prv_ = c.prv_, &pub_ = c.pub_;
+            std::vector<uint64_t> mid_at(K), prv_at(K), pub_at(K);
+            for (size_t k = 0; k < K; k++) {
+                uint64_t cnt = kind_first[k + 1] - kind_first[k];
+                mid_at[k] = n_mid, prv_at[k] = n_prv, pub_at[k] = n_pub;
+                n_mid += cnt * iface_.count(k), n_prv += cnt * prv_.count(k), n_pub += cnt * pub_.count(k);
+            }
+            // nVar checks of encode_statement_common (libs/src/group_structures/mod.rs:231-264, 294-296), over ALL placements
+            {
+                std::vector<PlacementVariables> shape(P);
+                uint64_t all_mid = 0, all_prv = 0;
+                for (size_t q = 0; q < P; q++) shape[q].subcircuitId = W.id[q], all_mid += iface_.count(W.id[q]), all_prv += prv_.count(W.id[q]);
+                if (all_mid != count_o_mid_nvar(shape, c.infos) || all_prv != count_o_prv_nvar(shape, c.infos)) throw Error("nVar mismatch while encoding statement");
+            }
+            if (n_mid >= (1ull << 31) || n_prv >= (1ull << 31)) throw Error("binding commitment too large");
+            b_ev = DeviceVec<ScalarField>(m_i * lc);
+            if (binding_lists) {
+                mid_sc = DeviceVec<ScalarField>(n_mid + 1), prv_sc = DeviceVec<ScalarField>(n_prv + 1), pub_sc = DeviceVec<ScalarField>(n_pub + 1);
+                mid_ix = DeviceVec<uint32_t>(n_mid + 1), prv_ix = DeviceVec<uint32_t>(n_prv + 1), pub_ix = DeviceVec<uint32_t>(n_pub + 1);
+            }
+            if (m_i * lc) check(tkmk_memset(b_ev.ptr(), 0, m_i * lc * sizeof(ScalarField)), "memset");
+            for (size_t k = 0; k < K; k++) {
+                uint32_t cnt = kind_first[k + 1] - kind_first[k];
+                if (!cnt) continue;
+                const uint64_t *vo = d_offs.ptr() + kind_first[k];
+                const uint32_t *sl = d_slots.ptr() + kind_first[k], *gsl = d_gslots.ptr() + kind_first[k];
+                if (!binding_lists) {
+                    check(tkmk_witness_route(d_vars.ptr(), vo, sl, cnt, iface_.wire.ptr() + iface_.first[k], iface_.row.ptr() + iface_.first[k], iface_.count(k), b_ev.ptr(),
+                                             (uint32_t)lc, nullptr, nullptr, 0, 0, nullptr),
+                          "tkmk_witness_route");
+                    continue;
+                }
+                if (sh.world == 1) {
+                    check(tkmk_witness_route(d_vars.ptr(), vo, sl, cnt, iface_.wire.ptr() + iface_.first[k], iface_.row.ptr() + iface_.first[k], iface_.count(k), b_ev.ptr(),
+                                             (uint32_t)s_max, mid_sc.ptr() + mid_at[k], mid_ix.ptr() + mid_at[k], (uint32_t)s_max, 1, nullptr),
+                          "tkmk_witness_route");
+                } else {
+                    // the interface matrix takes the LOCAL column of a placement, the binding table's row index its GLOBAL slot: two calls
+                    check(tkmk_witness_route(d_vars.ptr(), vo, sl, cnt, iface_.wire.ptr() + iface_.first[k], iface_.row.ptr() + iface_.first[k], iface_.count(k), b_ev.ptr(),
+                                             (uint32_t)lc, nullptr, nullptr, 0, 0, nullptr),
+                          "tkmk_witness_route");
+                    check(tkmk_witness_route(d_vars.ptr(), vo, gsl, cnt, iface_.wire.ptr() + iface_.first[k], iface_.row.ptr() + iface_.first[k], iface_.count(k), nullptr, 0,
+                                             mid_sc.ptr() + mid_at[k], mid_ix.ptr() + mid_at[k], (uint32_t)s_max, 1, nullptr),
+                          "tkmk_witness_route");
+                }
+                check(tkmk_witness_route(d_vars.ptr(), vo, gsl, cnt, prv_.wire.ptr() + prv_.first[k], prv_.row.ptr() + prv_.first[k], prv_.count(k), nullptr, 0,
+                                         prv_sc.ptr() + prv_at[k], prv_ix.ptr() + prv_at[k], (uint32_t)s_max, 1, nullptr),
+                      "tkmk_witness_route");
+                check(tkmk_witness_route(d_vars.ptr(), vo, gsl, cnt, pub_.wire.ptr() + pub_.first[k], pub_.row.ptr() + pub_.first[k], pub_.count(k), nullptr, 0,
+                                         pub_sc.ptr() + pub_at[k], pub_ix.ptr() + pub_at[k], 1, 0, nullptr),
+                      "tkmk_witness_route");
+            }
+        }
+        // the three sections of host/tkmk_witness_check.hpp over what the steps above have built (unsharded only); u / v / w: the grids,
+        // wherever the caller keeps them by now
+        bool run_check(const ScalarField *u_dev, const ScalarField *v_dev, const ScalarField *w_dev, const ScalarField *b_dev, witness_check::Report &rep) const {
+            witness_check::Inputs in;
+            in.sp = &c.sp, in.infos = &c.infos, in.layout = &W, in.staged = c.pinned_;
+            in.u = u_dev, in.v = v_dev, in.w = w_dev, in.b = b_dev;
+            in.perm = &perm, in.d_dst = d_dst.ptr(), in.d_x = d_x.ptr(), in.d_y = d_y.ptr();
+            in.a_pub_user = &a_pub_user, in.a_pub_block = &a_pub_block, in.a_pub_function = &a_pub_function;
+            return witness_check::run(in, rep);
+        }
+
+      private:
+        // (the helper signals as soon as the values are staged; unmapping the 88 MB document — milliseconds of page-table work — happens
+        // after the signal, beside the upload)
+        void start_reader(const std::string &synth_dir, bool with_function) {
+            read_ = staged_.get_future();
+            reader_.t = std::thread([this, synth_dir, with_function] {
+                std::unique_ptr<MappedFile> pv_file;
+                try {
+                    pv_file.reset(new MappedFile(synth_dir + "/placementVariables.json"));
+                    W = parse_placement_variables_fast(pv_file->data(), pv_file->size(), c.n_wires_, [&](uint64_t total) { return c.staging(total); }, c.threads, sh.world, sh.rank);
+                    host_trace("init: placementVariables.json parsed (%zu placements, %llu values kept)", W.id.size(), (unsigned long long)W.total);
+                    if (W.id.size() > c.sp.s_max) throw Error("placement_variables length exceeds s_max.");
+                    const json::Value jinst = json::read_file(synth_dir + "/instance.json");
+                    a_pub_user = hex_list(jinst.at("a_pub_user"));
+                    a_pub_block = hex_list(jinst.at("a_pub_block"));
+                    if (with_function) a_pub_function = hex_list(jinst.at("a_pub_function"));
+                    staged_.set_value();
+                } catch (...) {
+                    staged_.set_exception(std::current_exception());
+                }
+            });
+        }
+        std::promise<void> staged_;
+        std::future<void> read_;
+        struct Joined {
+            std::thread t;
+            ~Joined() { if (t.joinable()) t.join(); }
+        } reader_;   // the last member: joined before anything the helper writes to goes
+    };
+
+    // TKMK_PROVER_CHECK_WITNESS (host/tkmk_witness_check.hpp) failed inside init: INVALID_ARGUMENT, like every input the documents decide
+    static Error witness_refused(const witness_check::Report &rep) { return Error("the witness failed its check (TKMK_PROVER_CHECK_WITNESS): " + rep.reason); }
+
+    // The witness check on its own: the loader's steps without the binding lists, then the three sections.  Own device buffers; nothing of
+    // a context's proving state is read or written (a context from open_circuit has none).  Not on a sharded context: the copy section
+    // compares cells of different columns, which live on different ranks.
+    bool check_witness(const std::string &synth_dir, witness_check::Report &rep) {
+        if (link) throw Error("check_witness: not available on a sharded context (the copy section crosses columns: it would need a collective)");
+        const double t0 = Prover::now();
+        WitnessLoader L(*this, synth_dir, true);
+        L.upload_permutation();
+        L.join();
+        rep.parse_s = Prover::now() - t0;
+        const double t1 = Prover::now();
+        L.upload();
+        rep.upload_s = Prover::now() - t1;
+        const double t2 = Prover::now();
+        L.eval_uvw();
+        L.route(false);
+        check(tkmk_device_synchronize(), "synchronize");
+        rep.build_s = Prover::now() - t2;
+        const double t3 = Prover::now();
+        const bool ok = L.run_check(L.u.ptr(), L.v.ptr(), L.w.ptr(), L.b_ev.ptr(), rep);
+        rep.check_s = Prover::now() - t3;
+        rep.total_s = Prover::now() - t0;
+        return ok;
+    }
+
+    // Prover::init (prove/src/lib.rs:675-1206) from the synthesizer's directory
+    // pending (optional): when given and this context is not sharded, the binding batch is left running and *pending holds it (it borrows
+    // the returned prover's a_free_X); finish_binding() completes the returned Binding later.  Otherwise the Binding is complete on return.
+    std::pair<std::unique_ptr<Prover>, Binding> init(const std::string &synth_dir, const Mixer &mixer, ProveTiming &tm, CommitBatch::Pending *pending = nullptr) {
+        using namespace prover_detail;
+        const double t0 = Prover::now();
+        const size_t n = sp.n, s_max = sp.s_max;
+        host_trace("init: begin");
+        // TKMK_PROVER_CHECK_WITNESS=1 (unsharded contexts): the three sections of host/tkmk_witness_check.hpp on the grids built below, before
+        // the binding commitments are issued.  Unset or 0: nothing is launched, nothing is downloaded.  A sharded context does not read it.
+        const bool checked = !link && witness_check::requested_at_prove();
+
+        // ---- the three per-proof documents (WitnessLoader): the helper reads the witness while this thread builds the permutation's two
+        // polynomials
+        std::unique_ptr<Prover> p(new Prover());
+        p->sp = sp, p->m_i = m_i, p->sigma = sigma.get(), p->mixer = mixer, p->lagrange = lagrange_;
+        if (!link) {
+            if (!commit_stream_) check(tkmk_stream_create(&commit_stream_), "stream_create");
+            p->commit_stream = commit_stream_;
+        }
+        WitnessLoader L(*this, synth_dir, checked);
+        {
+            DeviceVec<ScalarField> e0 = s0_identity_.clone(), e1 = s1_identity_.clone();
+            L.upload_permutation();
+            if (!L.dst().empty()) {
+                const size_t entries = L.dst().size();
+                check(tkmk_fr_scatter_table(xp_.ptr(), xp_.len(), L.d_x.ptr(), L.d_dst.ptr(), entries, e0.ptr(), e0.len(), nullptr), "tkmk_fr_scatter_table");
+                check(tkmk_fr_scatter_table(yp_.ptr(), yp_.len(), L.d_y.ptr(), L.d_dst.ptr(), entries, e1.ptr(), e1.len(), nullptr), "tkmk_fr_scatter_table");
+            }
+            p->s0XY = Poly::from_rou_evals_cols(e0, m_i, s_max), p->s1XY = Poly::from_rou_evals_cols(e1, m_i, s_max);
+            p->s0_ev = std::move(e0), p->s1_ev = std::move(e1);   // prove1 forms f and g on the grid from these
+            p->s0_identity = &s0_identity_, p->s1_identity = &s1_identity_;
+        }
+        host_trace("init: s0 / s1 issued");
+        L.join();
         tm.parse = Prover::now() - t0;
 
         // ---- one upload of the witness and of the small index arrays
         const double t1 = Prover::now();
-        DeviceVec<ScalarField> d_vars((size_t)W.total + 1);
-        if (W.total) check(tkmk_memcpy_h2d(d_vars.ptr(), pinned_, (size_t)W.total * sizeof(ScalarField)), "witness upload");
-        DeviceVec<uint32_t> d_id = DeviceVec<uint32_t>::from_host(ids_local);
-        DeviceVec<uint64_t> d_off = DeviceVec<uint64_t>::from_host(offs_local);
-        DeviceVec<uint32_t> d_slots = DeviceVec<uint32_t>::from_host(slots), d_gslots = DeviceVec<uint32_t>::from_host(gslots);
-        DeviceVec<uint64_t> d_offs = DeviceVec<uint64_t>::from_host(offs);
+        L.upload();
         tm.upload = Prover::now() - t1;
 
         // ---- polynomials
         const double t2 = Prover::now();
-        {   // read_R1CS_gen_uvwXY (libs/src/iotools/mod.rs:1287-1420): one column per placement — this rank's placements, its columns
-            DeviceVec<ScalarField> u(n * lc), v(n * lc), w(n * lc);
-            check(tkmk_r1cs_library_eval(lib_, d_vars.ptr(), d_id.ptr(), d_off.ptr(), (uint32_t)PL, (uint32_t)n, (uint32_t)lc, u.ptr(), v.ptr(), w.ptr(), nullptr),
-                  "tkmk_r1cs_library_eval");
-            p->uXY = Poly::from_rou_evals_cols(u, n, s_max), p->vXY = Poly::from_rou_evals_cols(v, n, s_max), p->wXY = Poly::from_rou_evals_cols(w, n, s_max);
-            if (lagrange_n_) p->u_ev = std::move(u), p->v_ev = std::move(v), p->w_ev = std::move(w);   // prove0 commits from these
-        }
-        // gen_bXY + the (scalar, CRS row) lists of O_mid / O_prv / O_pub_free, kind by kind
-        uint64_t n_mid = 0, n_prv = 0, n_pub = 0;
-        std::vector<uint64_t> mid_at(K), prv_at(K), pub_at(K);
-        for (size_t k = 0; k < K; k++) {
-            uint64_t cnt = kind_first[k + 1] - kind_first[k];
-            mid_at[k] = n_mid, prv_at[k] = n_prv, pub_at[k] = n_pub;
-            n_mid += cnt * iface_.count(k), n_prv += cnt * prv_.count(k), n_pub += cnt * pub_.count(k);
-        }
-        // nVar checks of encode_statement_common (libs/src/group_structures/mod.rs:231-264, 294-296), over ALL placements
-        {
-            std::vector<PlacementVariables> shape(P);
-            uint64_t all_mid = 0, all_prv = 0;
-            for (size_t q = 0; q < P; q++) shape[q].subcircuitId = W.id[q], all_mid += iface_.count(W.id[q]), all_prv += prv_.count(W.id[q]);
-            if (all_mid != count_o_mid_nvar(shape, infos) || all_prv != count_o_prv_nvar(shape, infos)) throw Error("nVar mismatch while encoding statement");
-        }
-        if (n_mid >= (1ull << 31) || n_prv >= (1ull << 31)) throw Error("binding commitment too large");
-        DeviceVec<ScalarField> b_ev(m_i * lc), mid_sc(n_mid + 1), prv_sc(n_prv + 1), pub_sc(n_pub + 1);
-        DeviceVec<uint32_t> mid_ix(n_mid + 1), prv_ix(n_prv + 1), pub_ix(n_pub + 1);
-        if (m_i * lc) check(tkmk_memset(b_ev.ptr(), 0, m_i * lc * sizeof(ScalarField)), "memset");
-        for (size_t k = 0; k < K; k++) {
-            uint32_t cnt = kind_first[k + 1] - kind_first[k];
-            if (!cnt) continue;
-            const uint64_t *vo = d_offs.ptr() + kind_first[k];
-            const uint32_t *sl = d_slots.ptr() + kind_first[k], *gsl = d_gslots.ptr() + kind_first[k];
-            if (sh.world == 1) {
-                check(tkmk_witness_route(d_vars.ptr(), vo, sl, cnt, iface_.wire.ptr() + iface_.first[k], iface_.row.ptr() + iface_.first[k], iface_.count(k), b_ev.ptr(),
-                                         (uint32_t)s_max, mid_sc.ptr() + mid_at[k], mid_ix.ptr() + mid_at[k], (uint32_t)s_max, 1, nullptr),
-                      "tkmk_witness_route");
-            } else {
-                // the interface matrix takes the LOCAL column of a placement, the binding table's row index its GLOBAL slot: two calls
-                check(tkmk_witness_route(d_vars.ptr(), vo, sl, cnt, iface_.wire.ptr() + iface_.first[k], iface_.row.ptr() + iface_.first[k], iface_.count(k), b_ev.ptr(),
-                                         (uint32_t)lc, nullptr, nullptr, 0, 0, nullptr),
-                      "tkmk_witness_route");
-                check(tkmk_witness_route(d_vars.ptr(), vo, gsl, cnt, iface_.wire.ptr() + iface_.first[k], iface_.row.ptr() + iface_.first[k], iface_.count(k), nullptr, 0,
-                                         mid_sc.ptr() + mid_at[k], mid_ix.ptr() + mid_at[k], (uint32_t)s_max, 1, nullptr),
-                      "tkmk_witness_route");
-            }
-            check(tkmk_witness_route(d_vars.ptr(), vo, gsl, cnt, prv_.wire.ptr() + prv_.first[k], prv_.row.ptr() + prv_.first[k], prv_.count(k), nullptr, 0,
-                                     prv_sc.ptr() + prv_at[k], prv_ix.ptr() + prv_at[k], (uint32_t)s_max, 1, nullptr),
-                  "tkmk_witness_route");
-            check(tkmk_witness_route(d_vars.ptr(), vo, gsl, cnt, pub_.wire.ptr() + pub_.first[k], pub_.row.ptr() + pub_.first[k], pub_.count(k), nullptr, 0,
-                                     pub_sc.ptr() + pub_at[k], pub_ix.ptr() + pub_at[k], 1, 0, nullptr),
-                  "tkmk_witness_route");
-        }
+        L.eval_uvw();
+        p->uXY = Poly::from_rou_evals_cols(L.u, n, s_max), p->vXY = Poly::from_rou_evals_cols(L.v, n, s_max), p->wXY = Poly::from_rou_evals_cols(L.w, n, s_max);
+        if (lagrange_n_) p->u_ev = std::move(L.u), p->v_ev = std::move(L.v), p->w_ev = std::move(L.w);   // prove0 commits from these
+        else if (!checked) L.u = DeviceVec<ScalarField>(), L.v = DeviceVec<ScalarField>(), L.w = DeviceVec<ScalarField>();
+        L.route(true);
+        DeviceVec<ScalarField> &b_ev = L.b_ev, &mid_sc = L.mid_sc, &prv_sc = L.prv_sc, &pub_sc = L.pub_sc;
+        DeviceVec<uint32_t> &mid_ix = L.mid_ix, &prv_ix = L.prv_ix, &pub_ix = L.pub_ix;
+        const uint64_t n_mid = L.n_mid, n_prv = L.n_prv, n_pub = L.n_pub;
         p->bXY = Poly::from_rou_evals_cols(b_ev, m_i, s_max);
         p->b_ev = std::move(b_ev);   // prove1 forms f and g on the grid from it; with the Lagrange tables prove0 commits B from it too
         if (lagrange_mi_) p->lagrange_n = lagrange_n_.get(), p->lagrange_mi = lagrange_mi_, p->lagrange_mi_prefix = lagrange_mi_prefix_.get();
         p->rXY = Poly::zero();
-        p->a_free_X = gen_a_free_X(a_pub_user, a_pub_block, sp);
+        p->a_free_X = gen_a_free_X(L.a_pub_user, L.a_pub_block, sp);
         p->t_n = vanishing(n, true), p->t_mi = vanishing(m_i, true), p->t_smax = vanishing(s_max, false);
         check(tkmk_device_synchronize(), "synchronize");
         tm.build = Prover::now() - t2;
+        if (checked) {
+            witness_check::Report rep;
+            const bool kept = !lagrange_n_;   // the grids are the loader's still
+            if (!L.run_check(kept ? L.u.ptr() : p->u_ev.ptr(), kept ? L.v.ptr() : p->v_ev.ptr(), kept ? L.w.ptr() : p->w_ev.ptr(), p->b_ev.ptr(), rep)) throw witness_refused(rep);
+        }
 
         // ---- binding commitments (lib.rs:1086-1160): four MSMs over resident tables in one pipelined call
         const double t3 = Prover::now();

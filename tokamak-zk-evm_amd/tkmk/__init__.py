@@ -99,7 +99,7 @@ SYMBOLS = [
     "tkmk_poly_div_by_vanishing_opt", "tkmk_poly_div_by_ruffini", "tkmk_r1cs_eval_rows",
     "tkmk_msm_multi_ex", "tkmk_msm_segmented", "tkmk_msm_segmented_status", "bls12_381_msm_convert_bases", "tkmk_r1cs_library_create", "tkmk_r1cs_library_destroy", "tkmk_r1cs_library_eval",
     "tkmk_r1cs_library_mix", "tkmk_fr_outer",
-    "tkmk_witness_route", "tkmk_fr_scatter_table", "tkmk_msm_set_pipeline_streams", "tkmk_msm_get_pipeline_streams", "tkmk_host_malloc", "tkmk_host_free", "tkmk_stats_reset", "tkmk_stats_get",
+    "tkmk_witness_route", "tkmk_fr_scatter_table", "tkmk_witness_check_r1cs", "tkmk_witness_check_copy", "tkmk_msm_set_pipeline_streams", "tkmk_msm_get_pipeline_streams", "tkmk_host_malloc", "tkmk_host_free", "tkmk_stats_reset", "tkmk_stats_get",
     "bls12_381_ntt_domain_size", "bn254_ntt_domain_size", "tkmk_poly_lincomb", "tkmk_bintt_padded", "tkmk_diag_device_switch", "tkmk_diag_gather_probe",
     "bls12_381_get_root_of_unity_with_generator", "tkmk_ntt_root_generator", "tkmk_ntt_set_root_generator", "tkmk_poly_geometric_grid", "tkmk_crs_identify_root", "tkmk_g1_check",
     "bls12_381_generate_random_affine_points", "bls12_381_generate_scalars", "bls12_381_polynomial_add", "bls12_381_polynomial_clone", "bls12_381_polynomial_coeffs_device_ptr", "bls12_381_polynomial_copy_coeffs", "bls12_381_polynomial_create_from_coefficients", "bls12_381_polynomial_create_from_rou_evaluations", "bls12_381_polynomial_degree", "bls12_381_polynomial_delete", "bls12_381_polynomial_divide", "bls12_381_polynomial_evaluate", "bls12_381_polynomial_get_coeff", "bls12_381_polynomial_multiply", "bls12_381_polynomial_multiply_by_scalar", "bls12_381_polynomial_nof_coeffs", "bls12_381_polynomial_slice", "bls12_381_polynomial_subtract", "bls12_381_vector_accumulate",
@@ -834,6 +834,50 @@ def r1cs_library_mix(library, weights, cols, n, n_cols, out_stride=None, outs=No
     _check(lib().tkmk_r1cs_library_mix(library._h, wp, cp, ctypes.c_uint32(n), ctypes.c_uint32(n_cols), ctypes.c_uint32(out_stride), _p(outs[0]), _p(outs[1]),
                                        _p(outs[2]), None), "tkmk_r1cs_library_mix")
     return tuple(outs)
+
+
+# the witness check's two kernels (csrc/witcheck.hip): the argument lists of include/tkmk.h, in order (tests/test_witness_check_abi.py
+# compares them with the header)
+WITNESS_CHECK_ARGTYPES = {
+    "tkmk_witness_check_r1cs": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p],
+    "tkmk_witness_check_copy": [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p],
+}
+
+
+def _witness_check_fn(name):
+    fn = getattr(lib(), name)
+    fn.argtypes, fn.restype = WITNESS_CHECK_ARGTYPES[name], ctypes.c_int
+    return fn
+
+
+def witness_check_r1cs(u, v, w, n_rows, n_cols, stride=None, outs=None):
+    """tkmk_witness_check_r1cs over three DeviceBuffers of plain Fr, element (row, col) at row * stride + col: does u . v = w hold in every
+    cell of n_rows x n_cols?  -> (bad_count, first_bad_row, total_bad): two uint32 arrays of n_cols entries (failing rows per column; the
+    smallest failing row, 0xFFFFFFFF when none) and the sum of the counts.  outs: the two device arrays to write (n_cols uint32 each)"""
+    stride = n_cols if stride is None else stride
+    d_cnt, d_first = (DeviceBuffer(4 * max(n_cols, 1)), DeviceBuffer(4 * max(n_cols, 1))) if outs is None else outs
+    total = ctypes.c_uint64()
+    _check(_witness_check_fn("tkmk_witness_check_r1cs")(u.ptr, v.ptr, w.ptr, n_rows, n_cols, stride, d_cnt.ptr, d_first.ptr, ctypes.byref(total), None),
+           "tkmk_witness_check_r1cs")
+    return d_cnt.to_host(4 * n_cols).view(np.uint32).copy(), d_first.to_host(4 * n_cols).view(np.uint32).copy(), total.value
+
+
+def witness_check_copy(b, rows, cols, stride, dst_idx, src_x, src_y):
+    """tkmk_witness_check_copy over a DeviceBuffer of plain Fr (rows x cols cells, element (row, col) at row * stride + col): is
+    b[dst_idx[e]] = b[src_x[e] * stride + src_y[e]] for every entry?  -> (bad_entries, first_bad_entry or None, in_range): in_range is
+    False when some entry pointed outside the grid (TKMK_ERR_INVALID_ARGUMENT: that entry was skipped, the others judged)"""
+    arrs = [np.ascontiguousarray(a, np.uint32) for a in (dst_idx, src_x, src_y)]
+    n = arrs[0].size
+    assert arrs[1].size == n and arrs[2].size == n
+    dev = [DeviceBuffer.from_host(a.view(np.uint8)) if n else None for a in arrs]
+    bad, first = ctypes.c_uint64(), ctypes.c_uint64()
+    code = _witness_check_fn("tkmk_witness_check_copy")(b.ptr if b is not None else None, rows, cols, stride, *[d.ptr if d is not None else None for d in dev],
+                                                         n, ctypes.byref(bad), ctypes.byref(first), None)
+    if code not in (0, 11):
+        raise TkmkError(code, "tkmk_witness_check_copy")
+    return bad.value, (None if first.value == (1 << 64) - 1 else first.value), code == 0
 
 
 class ExprInstr(ctypes.Structure):
