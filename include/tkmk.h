@@ -697,13 +697,22 @@ tkmk_error tkmk_fr_scatter_table(const tkmk_fr *table_dev, uint64_t table_len, c
  * layout (dst_idx = row * stride + col).  *bad_entries_out = the number of entries whose two cells differ, *first_bad_entry_out = the
  * smallest such e, UINT64_MAX when there is none (both host).  An entry that points outside rows x cols is never dereferenced and takes
  * no part in the two results; the call then returns TKMK_ERR_INVALID_ARGUMENT after the valid entries were judged — the contract of
- * tkmk_fr_scatter_table.  n_entries = 0 is success with zero bad entries. */
+ * tkmk_fr_scatter_table.  n_entries = 0 is success with zero bad entries.
+ *
+ * _copy_split: the same comparison for one rank of a sharded prover, whose sources live on other ranks: for every entry e < n compares
+ * b_local[dst_local[e]] (this rank's own cells, local_cells of them) with sources[src_slot[e]] (the n_sources source values the ranks
+ * have gathered).  Results and conventions as _copy: an entry with dst_local >= local_cells or src_slot >= n_sources is never
+ * dereferenced, takes no part in the two results, and the call returns TKMK_ERR_INVALID_ARGUMENT after the others were judged; n = 0
+ * is success with 0 / UINT64_MAX.  Slots may repeat and come in any order. */
 tkmk_error tkmk_witness_check_r1cs(const tkmk_fr *u_dev, const tkmk_fr *v_dev, const tkmk_fr *w_dev, uint32_t n_rows, uint32_t n_cols,
                                    uint32_t stride, uint32_t *bad_count_dev, uint32_t *first_bad_row_dev, uint64_t *total_bad_out,
                                    tkmk_stream stream);
 tkmk_error tkmk_witness_check_copy(const tkmk_fr *b_dev, uint32_t rows, uint32_t cols, uint32_t stride, const uint32_t *dst_idx_dev,
                                    const uint32_t *src_x_dev, const uint32_t *src_y_dev, uint64_t n_entries, uint64_t *bad_entries_out,
                                    uint64_t *first_bad_entry_out, tkmk_stream stream);
+tkmk_error tkmk_witness_check_copy_split(const tkmk_fr *b_local_dev, uint64_t local_cells, const uint32_t *dst_local_dev,
+                                         const tkmk_fr *sources_dev, uint64_t n_sources, const uint32_t *src_slot_dev, uint64_t n,
+                                         uint64_t *bad_entries_out, uint64_t *first_bad_entry_out, tkmk_stream stream);
 /* pinned host memory for staging (HostSlice buffers the reference uploads from are pageable; pinned staging reaches link rate) */
 tkmk_error tkmk_host_malloc(void **ptr, size_t bytes);
 tkmk_error tkmk_host_free(void *ptr);

@@ -234,17 +234,32 @@ tkmk_error tkmk_crs_audit_circuit_files(const char *subcircuit_library_dir, cons
  * "subcircuitId", "name", "first_row", "bad_rows", "u", "v", "w"}]}, "copy": {"ok", "entries", "bijection", "hit_twice" ({"row", "col"},
  * present when not a bijection), "bad_entries", "first": [{"entry", "row", "col", "X", "Y", "value", "source"}]}, "public": {"ok", "wires",
  * "bad", "first": [{"index", "placement", "wire", "value", "instance"}]}, "seconds": {"parse", "upload", "build", "check", "total"}} — at
- * most 8 findings per section, field values as 0x + 64 hex digits.  Not covered: sharded contexts, BN254, WHICH variable of a failing row
- * is wrong. */
+ * most 8 findings per section, field values as 0x + 64 hex digits.  Sharded contexts: tkmk_prover_check_witness_sharded below.  Not
+ * covered: a sharded form of THIS entry or of bin/witness-check (there is no sharded context without a reference string), BN254, WHICH
+ * variable of a failing row is wrong. */
 tkmk_error tkmk_witness_check_files(const char *subcircuit_library_dir, const char *synthesizer_dir, int *ok, char **report_json_out);
 /* The same against a resident context's library (nothing is read from subcircuit_library_dir again): own device buffers, a turn on the
- * default stream like a proof, and nothing a later tkmk_prover_prove reads is changed.  On a context from tkmk_prover_open_sharded it
- * returns TKMK_ERR_INVALID_ARGUMENT: the copy section compares cells of different columns, which live on different ranks.
+ * default stream like a proof, and nothing a later tkmk_prover_prove reads is changed.  This entry is NOT collective: on a context from
+ * tkmk_prover_open_sharded it returns TKMK_ERR_INVALID_ARGUMENT (the copy section compares cells of different columns, which live on
+ * different ranks) and the message names tkmk_prover_check_witness_sharded.
  * TKMK_PROVER_CHECK_WITNESS=1 in the environment makes tkmk_prover_prove[_ex] (and bin/prove) run the three sections inside init, on the
  * grids it has just built, before the binding commitments are issued: a witness that fails is refused with TKMK_ERR_INVALID_ARGUMENT,
  * tkmk_prover_last_error() carries the report's "reason", no proof.json is written and the context stays usable.  Unset or 0: nothing is
- * launched and nothing is downloaded.  A sharded context does not read the variable. */
+ * launched, nothing is downloaded and (sharded) nothing is exchanged.  A sharded context reads the variable too — every rank must run
+ * with the same value: the check is the collective one below, a refusal is every rank's error with one and the same text, no rank writes
+ * proof.json, and the communicator is not aborted (the outcome is replicated), so the contexts stay usable. */
 tkmk_error tkmk_prover_check_witness(tkmk_prover *p, const char *synthesizer_dir, int *ok, char **report_json_out);
+/* The check on a sharded context: COLLECTIVE — every rank calls it with the same arguments, every rank gets the same *ok and the same
+ * report (byte for byte outside "seconds", the report of tkmk_prover_check_witness on a single-GPU context for the same documents).
+ * arithmetic and public are local to the rank that holds the placement; for copy every rank packs the source values the permutation
+ * asks of its columns, ONE tkmk_comm_all_gather_dev hands all of them to every rank (at most about one copy of b when the sources are
+ * spread evenly: m_I * s_max * 32 bytes), each rank compares its own destination cells (tkmk_witness_check_copy_split), and ONE
+ * tkmk_comm_all_gather_host merges the findings: two exchanges beyond the agreement on the parsed documents.  The contract is that of
+ * tkmk_prover_check_witness otherwise: own device buffers, nothing a later proof reads is changed, an unreadable document is every
+ * rank's error naming the file (the communicator lives on); a device or transport failure aborts the communicator, as in _prove.  On a
+ * context from tkmk_prover_open it is tkmk_prover_check_witness.  Not covered: BN254, WHICH variable of a failing row is wrong, an
+ * all-to-all in place of the all-gather. */
+tkmk_error tkmk_prover_check_witness_sharded(tkmk_prover *p, const char *synthesizer_dir, int *ok, char **report_json_out);
 
 #ifdef __cplusplus
 }

@@ -133,3 +133,61 @@ TK_API tkmk_error tkmk_witness_check_copy(const tkmk_fr *b_dev, uint32_t rows, u
     *bad_entries_out = res[0], *first_bad_entry_out = res[1];
     return res[2] ? TKMK_ERR_INVALID_ARGUMENT : TKMK_SUCCESS;
 }
+
+// The copy comparison of one rank of a sharded prover: the destination cells are this rank's own (b_local, its columns of b), the source
+// values arrive packed from every rank in one gathered buffer (host/tkmk_witness_check.hpp run_sharded).  One lane per entry, one 32-byte
+// load from each buffer (the destination indices ascend, the slots mostly do); an entry whose destination or slot lies outside its
+// buffer is never dereferenced and counted in res[2].  The reduction is k_witness_check_copy's: ballot, LDS, one atomicAdd and one
+// atomicMin per workgroup that saw a failure.
+__global__ __launch_bounds__(256) void k_witness_check_copy_split(const fr_t *__restrict__ b_local, uint64_t local_cells,
+                                                                 const uint32_t *__restrict__ dst_local, const fr_t *__restrict__ sources,
+                                                                 uint64_t n_sources, const uint32_t *__restrict__ src_slot, uint64_t n,
+                                                                 unsigned long long *__restrict__ res) {
+    __shared__ unsigned long long s_bad[4], s_first[4], s_inv[4];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    bool bad = false, invalid = false;
+    if (e < n) {
+        const uint32_t d = dst_local[e], s = src_slot[e];
+        if (d >= local_cells || s >= n_sources) invalid = true;
+        else bad = !Fr::eq(Fr::canon(tk_load(b_local + d)), Fr::canon(tk_load(sources + s)));
+    }
+    const unsigned long long m_bad = __ballot(bad), m_inv = __ballot(invalid);
+    if (lane == 0) {
+        s_bad[wave] = (unsigned long long)__popcll(m_bad);
+        s_first[wave] = m_bad ? e + (unsigned long long)(__ffsll((long long)m_bad) - 1) : ~0ull;
+        s_inv[wave] = (unsigned long long)__popcll(m_inv);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long nb = 0, ni = 0, first = ~0ull;
+        for (int k = 0; k < 4; k++) nb += s_bad[k], ni += s_inv[k], first = s_first[k] < first ? s_first[k] : first;
+        if (nb) atomicAdd(res + 0, nb), atomicMin(res + 1, first);
+        if (ni) atomicAdd(res + 2, ni);
+    }
+}
+
+TK_API tkmk_error tkmk_witness_check_copy_split(const tkmk_fr *b_local_dev, uint64_t local_cells, const uint32_t *dst_local_dev,
+                                                const tkmk_fr *sources_dev, uint64_t n_sources, const uint32_t *src_slot_dev, uint64_t n,
+                                                uint64_t *bad_entries_out, uint64_t *first_bad_entry_out, tkmk_stream stream) {
+    if (!bad_entries_out || !first_bad_entry_out) return TKMK_ERR_INVALID_POINTER;
+    *bad_entries_out = 0, *first_bad_entry_out = UINT64_MAX;
+    if (n == 0) return TKMK_SUCCESS;
+    if (!b_local_dev || !dst_local_dev || !sources_dev || !src_slot_dev) return TKMK_ERR_INVALID_POINTER;
+    if (n > (0x7FFFFFFFull << 8)) return TKMK_ERR_INVALID_ARGUMENT;   // one workgroup per 256 entries
+    TK_TRY(tk_require_device());
+    hipStream_t s = tk_stream(stream);
+    tk_frame frame(s);
+    tk_scratch d_res;
+    TK_TRY(d_res.alloc(3 * sizeof(unsigned long long), s));
+    const unsigned long long init[3] = {0ull, ~0ull, 0ull};
+    TK_HIP(hipMemcpyAsync(d_res.p, init, sizeof init, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_witness_check_copy_split, tk_div_up(n, 256), 256, 0, s, (const fr_t *)b_local_dev, local_cells, dst_local_dev,
+                       (const fr_t *)sources_dev, n_sources, src_slot_dev, n, d_res.as<unsigned long long>());
+    TK_HIP(hipGetLastError());
+    unsigned long long res[3] = {0, 0, 0};
+    TK_HIP(hipMemcpyAsync(res, d_res.p, sizeof res, hipMemcpyDeviceToHost, s));
+    TK_HIP(hipStreamSynchronize(s));
+    *bad_entries_out = res[0], *first_bad_entry_out = res[1];
+    return res[2] ? TKMK_ERR_INVALID_ARGUMENT : TKMK_SUCCESS;
+}

@@ -228,10 +228,24 @@ TKP_API tkmk_error tkmk_prover_check_witness(tkmk_prover *p, const char *synthes
     *ok = 0;
     if (report_json_out) *report_json_out = nullptr;
     return guarded([&] {
-        if (p->ctx->link) throw Error("tkmk_prover_check_witness: not available on a sharded context (the copy section crosses columns: it would need a collective)");
+        if (p->ctx->link)
+            throw Error("tkmk_prover_check_witness: not available on a sharded context (the copy section crosses columns, and this entry is not collective: every rank calls tkmk_prover_check_witness_sharded instead)");
         DefaultStreamTurn turn(false);
         witness_check::Report rep;
         const bool verdict = p->ctx->check_witness(synthesizer_dir, rep);
+        if (report_json_out) *report_json_out = dup_string(rep.to_json());
+        *ok = verdict ? 1 : 0;
+    });
+}
+// collective: every rank of a sharded context, with the same arguments (ProverContext::check_witness_sharded)
+TKP_API tkmk_error tkmk_prover_check_witness_sharded(tkmk_prover *p, const char *synthesizer_dir, int *ok, char **report_json_out) {
+    if (!p || !synthesizer_dir || !ok) return TKMK_ERR_INVALID_POINTER;
+    *ok = 0;
+    if (report_json_out) *report_json_out = nullptr;
+    return guarded([&] {
+        DefaultStreamTurn turn((bool)p->ctx->link);
+        witness_check::Report rep;
+        const bool verdict = p->ctx->check_witness_sharded(synthesizer_dir, rep);
         if (report_json_out) *report_json_out = dup_string(rep.to_json());
         *ok = verdict ? 1 : 0;
     });

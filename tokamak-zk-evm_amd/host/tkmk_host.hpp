@@ -123,6 +123,7 @@ struct ShardLink {
     decltype(&tkmk_comm_broadcast_host) broadcast_host = nullptr;
     decltype(&tkmk_comm_device_turn) device_turn = nullptr;
     decltype(&tkmk_comm_all_gather_host) all_gather_host = nullptr;
+    decltype(&tkmk_comm_all_gather_dev) all_gather_dev = nullptr;
     decltype(&tkmk_comm_agree) agree = nullptr;
     decltype(&tkmk_comm_abort) abort = nullptr;
     decltype(&tkmk_dist_fwd_cols_to_rows) fwd_cols_to_rows = nullptr;
@@ -153,6 +154,7 @@ struct ShardLink {
         };
         sym(l.multi_ex_sharded, "tkmk_msm_multi_ex_sharded"), sym(l.broadcast_host, "tkmk_comm_broadcast_host");
         sym(l.device_turn, "tkmk_comm_device_turn"), sym(l.all_gather_host, "tkmk_comm_all_gather_host");
+        sym(l.all_gather_dev, "tkmk_comm_all_gather_dev");
         sym(l.agree, "tkmk_comm_agree"), sym(l.abort, "tkmk_comm_abort");
         sym(l.fwd_cols_to_rows, "tkmk_dist_fwd_cols_to_rows"), sym(l.inv_rows_to_cols, "tkmk_dist_inv_rows_to_cols");
         sym(l.rows_rotate, "tkmk_dist_rows_rotate"), sym(l.ring_shift, "tkmk_comm_ring_shift");

@@ -367,6 +367,7 @@ class ProverContext {
         std::vector<ScalarField> a_pub_user, a_pub_block, a_pub_function;
         witness_check::EffectivePermutation perm;                      // the redirects of every rank's cells, global indices
         std::vector<uint32_t> local_dst, local_x, local_y;             // sharded: those of this rank's columns, local destinations
+        std::vector<uint32_t> local_entry;                             // ... and their indices into perm's arrays (ascending)
         DeviceVec<uint32_t> d_dst, d_x, d_y;                           // alive until the kernels reading them have run
         size_t P = 0, PL = 0;                                          // placements of the proof, and of this rank
         std::vector<uint32_t> kind_first, slots, gslots, ids_local;
@@ -400,6 +401,7 @@ class ProverContext {
                     const uint32_t row = perm.dst[e] / (uint32_t)s_max, col = perm.dst[e] % (uint32_t)s_max;
                     if (col % sh.world != sh.rank) continue;
                     local_dst.push_back(row * (uint32_t)lc + col / sh.world), local_x.push_back(perm.x[e]), local_y.push_back(perm.y[e]);
+                    local_entry.push_back((uint32_t)e);
                 }
         }
         void upload_permutation() {
@@ -512,15 +514,19 @@ class ProverContext {
                       "tkmk_witness_route");
             }
         }
-        // the three sections of host/tkmk_witness_check.hpp over what the steps above have built (unsharded only); u / v / w: the grids,
-        // wherever the caller keeps them by now
+        // the three sections of host/tkmk_witness_check.hpp over what the steps above have built; u / v / w: the grids, wherever the caller
+        // keeps them by now.  Sharded (world > 1): collective — this rank's columns, one device and one host all-gather, the same report on
+        // every rank (witness_check::run_sharded).
         bool run_check(const ScalarField *u_dev, const ScalarField *v_dev, const ScalarField *w_dev, const ScalarField *b_dev, witness_check::Report &rep) const {
             witness_check::Inputs in;
             in.sp = &c.sp, in.infos = &c.infos, in.layout = &W, in.staged = c.pinned_;
             in.u = u_dev, in.v = v_dev, in.w = w_dev, in.b = b_dev;
             in.perm = &perm, in.d_dst = d_dst.ptr(), in.d_x = d_x.ptr(), in.d_y = d_y.ptr();
             in.a_pub_user = &a_pub_user, in.a_pub_block = &a_pub_block, in.a_pub_function = &a_pub_function;
-            return witness_check::run(in, rep);
+            if (sh.world == 1) return witness_check::run(in, rep);
+            witness_check::ShardInputs si;
+            si.link = &c.link, si.lc = lc, si.placements = PL, si.local_entry = &local_entry, si.local_dst = &local_dst;
+            return witness_check::run_sharded(in, si, rep);
         }
 
       private:
@@ -557,10 +563,33 @@ class ProverContext {
     static Error witness_refused(const witness_check::Report &rep) { return Error("the witness failed its check (TKMK_PROVER_CHECK_WITNESS): " + rep.reason); }
 
     // The witness check on its own: the loader's steps without the binding lists, then the three sections.  Own device buffers; nothing of
-    // a context's proving state is read or written (a context from open_circuit has none).  Not on a sharded context: the copy section
-    // compares cells of different columns, which live on different ranks.
+    // a context's proving state is read or written (a context from open_circuit has none).  Not collective, so not on a sharded context:
+    // the copy section compares cells of different columns, which live on different ranks — check_witness_sharded is the entry for those.
     bool check_witness(const std::string &synth_dir, witness_check::Report &rep) {
-        if (link) throw Error("check_witness: not available on a sharded context (the copy section crosses columns: it would need a collective)");
+        if (link) throw Error("check_witness: not available on a sharded context (the copy section crosses columns: every rank calls check_witness_sharded instead)");
+        return check_witness_steps(synth_dir, rep);
+    }
+    // The same as a COLLECTIVE call: every rank of a sharded context calls it with the same arguments and gets the same verdict and report
+    // (the "seconds" are each rank's own).  Beyond the loader's agree: one device all-gather (the copy section's source values) and one
+    // host all-gather (the findings).  An unsharded context: check_witness.  Failures follow prove: what the replicated documents decide
+    // is every rank's error and the communicator lives on; a device or transport failure aborts it.
+    bool check_witness_sharded(const std::string &synth_dir, witness_check::Report &rep) {
+        if (!link) return check_witness(synth_dir, rep);
+        ShardSpan span(link);
+        try {
+            return check_witness_steps(synth_dir, rep);
+        } catch (const Error &e) {
+            const bool replicated_cause = e.code == TKMK_ERR_INVALID_ARGUMENT || e.code == TKMK_ERR_INVALID_POINTER;
+            if (link.shard.world > 1 && !replicated_cause) (void)link.abort(link.comm);
+            throw;
+        } catch (...) {
+            if (link.shard.world > 1) (void)link.abort(link.comm);
+            throw;
+        }
+    }
+
+  private:
+    bool check_witness_steps(const std::string &synth_dir, witness_check::Report &rep) {
         const double t0 = Prover::now();
         WitnessLoader L(*this, synth_dir, true);
         L.upload_permutation();
@@ -581,6 +610,8 @@ class ProverContext {
         return ok;
     }
 
+  public:
+
     // Prover::init (prove/src/lib.rs:675-1206) from the synthesizer's directory
     // pending (optional): when given and this context is not sharded, the binding batch is left running and *pending holds it (it borrows
     // the returned prover's a_free_X); finish_binding() completes the returned Binding later.  Otherwise the Binding is complete on return.
@@ -589,9 +620,11 @@ class ProverContext {
         const double t0 = Prover::now();
         const size_t n = sp.n, s_max = sp.s_max;
         host_trace("init: begin");
-        // TKMK_PROVER_CHECK_WITNESS=1 (unsharded contexts): the three sections of host/tkmk_witness_check.hpp on the grids built below, before
-        // the binding commitments are issued.  Unset or 0: nothing is launched, nothing is downloaded.  A sharded context does not read it.
-        const bool checked = !link && witness_check::requested_at_prove();
+        // TKMK_PROVER_CHECK_WITNESS=1: the three sections of host/tkmk_witness_check.hpp on the grids built below, before the binding
+        // commitments are issued.  Unset or 0: nothing is launched, nothing is downloaded, nothing is exchanged.  Sharded: every rank reads
+        // the same environment; the check's two all-gathers give every rank the same report, so a refusal is every rank's, with one text,
+        // and the communicator lives on.
+        const bool checked = witness_check::requested_at_prove();
 
         // ---- the three per-proof documents (WitnessLoader): the helper reads the witness while this thread builds the permutation's two
         // polynomials

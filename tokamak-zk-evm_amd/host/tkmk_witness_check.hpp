@@ -10,9 +10,28 @@
 // The reference has these diagnostics behind its `testing-mode` feature, as host loops over downloaded evaluations (prove/src/lib.rs:916-1017
 // flag_b / flag_s0 / flag_s1 / flag_r, 1472-1518 "Placement indexed at {} does not satisfy R1CS").  What "wrong" means is what the verifier
 // refuses: `ok` here equals tkmk_prover_verify's verdict on the proof the unguarded prover makes from the same documents
-// (tests/test_gpu_witness_check.py).  Not covered: sharded contexts (the copy section crosses columns), BN254, and WHICH variable of a
-// failing row is wrong.
+// (tests/test_gpu_witness_check.py).
+//
+// One proof over G ranks (run_sharded; ProverContext::check_witness_sharded and the knob inside a sharded init): a rank holds the columns
+// c = rank mod G of u, v, w, b, so arithmetic and public are local — a placement is a column, and only its owner staged its values — while
+// a copy entry ties cell (row, col) on rank col mod G to cell (X, Y) on rank Y mod G.  Every rank knows the whole effective permutation,
+// so every rank knows, without a message, the list S_s of entries whose source lives on rank s (entry order).  Rank s packs those values
+// of its b (tkmk_gather_rows_device), ONE tkmk_comm_all_gather_dev of max_s |S_s| values per rank gives every rank all of them, and each
+// rank compares its own destination cells against its slots of the gathered buffer (tkmk_witness_check_copy_split).  A rank receives
+// G * max_s |S_s| * 32 bytes.  The destinations are distinct, so the sum of the |S_s| is at most the number of cells: evenly spread sources
+// make the payload at most one copy of b (m_I * s_max * 32 bytes, 128 MB at BASELINE.json configs[3]); the padding to the longest list
+// costs more when the sources crowd onto few ranks.  Then ONE tkmk_comm_all_gather_host carries a fixed-size block per rank (counters, at most
+// MAX_FINDINGS findings per section, an error text) and every rank merges all blocks into the same report: totals summed, findings in the
+// order the unsharded code enumerates them (placement; entry; placement, wire), cut to MAX_FINDINGS.  An input error only one rank can
+// see (the public wires of placement 2 exist on its owner alone) travels in the block and is every rank's error, with one text.
+//
+// Not covered: a sharded bin/witness-check / tkmk_witness_check_files (there is no sharded context without a reference string), BN254,
+// WHICH variable of a failing row is wrong, and an all-to-all in place of the all-gather (a rank needs only the sources of its own
+// entries; the all-gather is the collective that exists on both transports).
 #pragma once
+#include <algorithm>
+#include <cstring>
+
 #include "tkmk_circuit.hpp"
 #include "tkmk_fastparse.hpp"
 #include "tkmk_host.hpp"
@@ -234,11 +253,12 @@ inline void check_copy(const Inputs &in, Report &rep) {
 
 // the public wires of the four buffer placements (encode_O_pub_free / encode_O_pub_fix, libs/src/group_structures/mod.rs:145-229: the outputs
 // of bufferPubOut, the inputs of bufferPubIn / bufferBlockIn / bufferEVMIn) against a_pub_user ++ a_pub_block ++ a_pub_function
-inline void check_public(const Inputs &in, Report &rep) {
+// (first, step): the placements q = first, first + step, ... — all of them, or those of one rank of a sharded prover
+inline void check_public(const Inputs &in, Report &rep, size_t first = 0, size_t step = 1) {
     const SetupParams &sp = *in.sp;
     auto &sec = rep.pub;
     const size_t P = std::min<size_t>(4, in.layout->id.size());
-    for (size_t q = 0; q < P; q++) {
+    for (size_t q = first; q < P; q += step) {
         const SubcircuitInfo &info = in.infos->at(in.layout->id[q]);
         const std::array<size_t, 2> *rng = nullptr;
         if (info.name == "bufferPubOut") rng = &info.Out_idx;
@@ -261,10 +281,8 @@ inline void check_public(const Inputs &in, Report &rep) {
     sec.ok = sec.bad == 0;
 }
 
-inline bool run(const Inputs &in, Report &rep) {
-    check_arithmetic(in, rep);
-    check_copy(in, rep);
-    check_public(in, rep);
+// the verdict and `reason` from the three sections' findings
+inline bool conclude(Report &rep) {
     rep.ok = rep.arithmetic.ok && rep.copy.ok && rep.pub.ok;
     rep.reason.clear();
     if (!rep.arithmetic.ok) {
@@ -288,5 +306,187 @@ inline bool run(const Inputs &in, Report &rep) {
     return rep.ok;
 }
 
+inline bool run(const Inputs &in, Report &rep) {
+    check_arithmetic(in, rep);
+    check_copy(in, rep);
+    check_public(in, rep);
+    return conclude(rep);
+}
+
+// ---- one proof over G ranks (see the head of this file) ----
+// What a rank of a sharded prover adds to Inputs, whose device pointers are then this rank's columns (u, v, w: n x lc, b: m_I x lc, element
+// (row, local column k) at row * lc + k; local column k is global column rank + k G), whose `perm` is the replicated whole and whose
+// d_dst holds the local destinations; d_x / d_y are not read.
+struct ShardInputs {
+    const ShardLink *link = nullptr;
+    size_t lc = 0, placements = 0;                         // this rank's columns of s_max, and its placements (the first `placements` columns)
+    const std::vector<uint32_t> *local_entry = nullptr;    // this rank's entries: index into perm's arrays, ascending ...
+    const std::vector<uint32_t> *local_dst = nullptr;      // ... and their destinations row * lc + col / G
+};
+
+// the block a rank contributes to the merge: plain data of one size on every rank
+struct ShardBlock {
+    struct Arithmetic {
+        uint64_t placement;
+        uint32_t first_row, bad_rows;
+        ScalarField u, v, w;
+    };
+    struct Copy {
+        uint64_t entry;
+        ScalarField value, source;
+    };
+    struct Public {
+        uint64_t index, placement, wire;
+        ScalarField value, instance;
+    };
+    uint64_t bad_cells, bad_placements, n_arithmetic;
+    uint64_t bad_entries, n_copy;
+    uint64_t wires, bad_public, n_public;
+    Arithmetic arithmetic[MAX_FINDINGS];
+    Copy copy[MAX_FINDINGS];
+    Public pub[MAX_FINDINGS];
+    uint32_t failed, failed_placement;   // an input error this rank alone could see, in that placement: `error` holds its text
+    char error[248];
+};
+static_assert(std::is_trivially_copyable<ShardBlock>::value, "ShardBlock travels as bytes");
+
+// this rank's columns of the arithmetic section: local column k is placement rank + k G
+inline void shard_arithmetic(const Inputs &in, const ShardInputs &sh, ShardBlock &blk) {
+    const size_t n = in.sp->n, PL = sh.placements, G = sh.link->shard.world, rank = sh.link->shard.rank;
+    if (!PL) return;
+    DeviceVec<uint32_t> d_cnt(PL), d_first(PL);
+    check(tkmk_witness_check_r1cs(in.u, in.v, in.w, (uint32_t)n, (uint32_t)PL, (uint32_t)sh.lc, d_cnt.ptr(), d_first.ptr(), &blk.bad_cells, nullptr), "tkmk_witness_check_r1cs");
+    if (!blk.bad_cells) return;
+    std::vector<uint32_t> cnt(PL), first(PL);
+    d_cnt.copy_to_host(cnt.data(), PL), d_first.copy_to_host(first.data(), PL);
+    for (size_t k = 0; k < PL; k++) {
+        if (!cnt[k]) continue;
+        blk.bad_placements++;
+        if (blk.n_arithmetic >= MAX_FINDINGS) continue;
+        ShardBlock::Arithmetic &f = blk.arithmetic[blk.n_arithmetic++];
+        f.placement = rank + k * G, f.first_row = first[k], f.bad_rows = cnt[k];
+        const size_t at = (size_t)first[k] * sh.lc + k;
+        check(tkmk_memcpy_d2h(&f.u, in.u + at, sizeof(ScalarField)), "memcpy_d2h");
+        check(tkmk_memcpy_d2h(&f.v, in.v + at, sizeof(ScalarField)), "memcpy_d2h");
+        check(tkmk_memcpy_d2h(&f.w, in.w + at, sizeof(ScalarField)), "memcpy_d2h");
+    }
+}
+
+// the values of the copy section: the one device all-gather, then this rank's entries against the gathered sources
+inline void shard_copy_values(const Inputs &in, const ShardInputs &sh, ShardBlock &blk) {
+    const size_t m_i = in.sp->m_i(), G = sh.link->shard.world, rank = sh.link->shard.rank, lc = sh.lc;
+    const EffectivePermutation &ep = *in.perm;
+    const size_t E = ep.dst.size();
+    // S_s, from the replicated arrays alone: entry e is number pos[e] of the entries whose source column Y lives on rank Y mod G
+    std::vector<uint32_t> pos(E), count(G, 0), mine;
+    for (size_t e = 0; e < E; e++) {
+        const uint32_t owner = ep.y[e] % (uint32_t)G;
+        pos[e] = count[owner]++;
+        if (owner == rank) mine.push_back(ep.x[e] * (uint32_t)lc + ep.y[e] / (uint32_t)G);   // the source cell in this rank's b
+    }
+    const size_t pad = *std::max_element(count.begin(), count.end());
+    if (!pad) return;   // no entry anywhere: every rank returns here
+    if (G * pad >= (1ull << 32)) throw Error("witness check: more gathered source values than a 32-bit slot can name");
+    DeviceVec<ScalarField> send(pad), sources(G * pad);
+    check(tkmk_memset(send.ptr(), 0, pad * sizeof(ScalarField)), "memset");
+    if (!mine.empty()) {
+        DeviceVec<uint32_t> d_mine = DeviceVec<uint32_t>::from_host(mine);
+        check(tkmk_gather_rows_device(in.b, sizeof(ScalarField), d_mine.ptr(), mine.size(), send.ptr(), nullptr), "tkmk_gather_rows_device");
+        check(tkmk_device_synchronize(), "synchronize");   // d_mine goes here
+    }
+    check(sh.link->all_gather_dev(sh.link->comm, send.ptr(), pad * sizeof(ScalarField), sources.ptr()), "tkmk_comm_all_gather_dev");
+    const std::vector<uint32_t> &entry = *sh.local_entry, &dst = *sh.local_dst;
+    const size_t n = entry.size();
+    if (!n) return;
+    std::vector<uint32_t> slot(n);
+    for (size_t k = 0; k < n; k++) slot[k] = (ep.y[entry[k]] % (uint32_t)G) * (uint32_t)pad + pos[entry[k]];
+    DeviceVec<uint32_t> d_slot = DeviceVec<uint32_t>::from_host(slot);
+    // the first MAX_FINDINGS failing entries of this rank, as check_copy finds them: the local lists ascend in the global entry index
+    uint64_t from = 0;
+    while (from < n) {
+        uint64_t bad = 0, first = UINT64_MAX;
+        check(tkmk_witness_check_copy_split(in.b, m_i * lc, in.d_dst + from, sources.ptr(), G * pad, d_slot.ptr() + from, n - from, &bad, &first, nullptr),
+              "tkmk_witness_check_copy_split");
+        if (from == 0) blk.bad_entries = bad;
+        if (!bad || blk.n_copy >= MAX_FINDINGS) break;
+        const uint64_t k = from + first;
+        ShardBlock::Copy &f = blk.copy[blk.n_copy++];
+        f.entry = entry[k];
+        check(tkmk_memcpy_d2h(&f.value, in.b + dst[k], sizeof(ScalarField)), "memcpy_d2h");
+        check(tkmk_memcpy_d2h(&f.source, sources.ptr() + slot[k], sizeof(ScalarField)), "memcpy_d2h");
+        from = k + 1;
+    }
+}
+
+// The three sections on rank link->shard.rank of G > 1; collective: every rank calls it, every rank gets the same report and verdict.
+// Exchanges: one tkmk_comm_all_gather_dev (none when the permutation is empty) and one tkmk_comm_all_gather_host.  A device or transport
+// failure leaves as an exception with the peers possibly waiting: the caller aborts the communicator (ProverContext does).
+inline bool run_sharded(const Inputs &in, const ShardInputs &sh, Report &rep) {
+    const size_t s_max = in.sp->s_max, G = sh.link->shard.world, rank = sh.link->shard.rank;
+    ShardBlock blk;
+    std::memset(&blk, 0, sizeof blk);
+    shard_arithmetic(in, sh, blk);
+    shard_copy_values(in, sh, blk);
+    {
+        Report own;   // placement q < 4 is checked by rank q mod G, the only one that staged its values; one placement per call
+        for (size_t q = rank; q < 4 && !blk.failed; q += G) {
+            try {
+                check_public(in, own, q, 4);
+            } catch (const Error &e) {
+                if (e.code != TKMK_ERR_INVALID_ARGUMENT) throw;
+                blk.failed = 1, blk.failed_placement = (uint32_t)q;
+                snprintf(blk.error, sizeof blk.error, "%s", e.what());
+            }
+        }
+        blk.wires = own.pub.wires, blk.bad_public = own.pub.bad, blk.n_public = own.pub.first.size();
+        for (size_t k = 0; k < own.pub.first.size(); k++) {
+            const PublicFinding &f = own.pub.first[k];
+            blk.pub[k] = ShardBlock::Public{f.index, f.placement, f.wire, f.value, f.instance};
+        }
+    }
+    std::vector<ShardBlock> all(G);
+    check(sh.link->all_gather_host(sh.link->comm, &blk, sizeof blk, all.data()), "tkmk_comm_all_gather_host");
+    const ShardBlock *failed = nullptr;   // the text of the lowest failing placement, as the unsharded walk would meet it, on every rank
+    for (const ShardBlock &b : all)
+        if (b.failed && (!failed || b.failed_placement < failed->failed_placement)) failed = &b;
+    if (failed) throw Error(std::string(failed->error, strnlen(failed->error, sizeof failed->error)));
+
+    // ---- the merge: the same on every rank
+    rep.arithmetic.placements = in.layout->id.size();
+    rep.copy.entries = in.perm->dst.size();
+    uint32_t twice = 0;
+    rep.copy.bijection = is_bijection(*in.perm, s_max, &twice);   // over the replicated arrays: no exchange, the same answer everywhere
+    rep.copy.twice_row = twice / (uint32_t)s_max, rep.copy.twice_col = twice % (uint32_t)s_max;
+    std::vector<ShardBlock::Arithmetic> fa;
+    std::vector<ShardBlock::Copy> fc;
+    std::vector<ShardBlock::Public> fp;
+    for (const ShardBlock &b : all) {
+        rep.arithmetic.bad_cells += b.bad_cells, rep.arithmetic.bad_placements += b.bad_placements;
+        rep.copy.bad_entries += b.bad_entries;
+        rep.pub.wires += b.wires, rep.pub.bad += b.bad_public;
+        if (b.n_arithmetic > MAX_FINDINGS || b.n_copy > MAX_FINDINGS || b.n_public > MAX_FINDINGS) throw Error(TKMK_ERR_UNKNOWN, "witness check: a rank's block is malformed");
+        fa.insert(fa.end(), b.arithmetic, b.arithmetic + b.n_arithmetic);
+        fc.insert(fc.end(), b.copy, b.copy + b.n_copy);
+        fp.insert(fp.end(), b.pub, b.pub + b.n_public);
+    }
+    std::sort(fa.begin(), fa.end(), [](const ShardBlock::Arithmetic &a, const ShardBlock::Arithmetic &b) { return a.placement < b.placement; });
+    std::sort(fc.begin(), fc.end(), [](const ShardBlock::Copy &a, const ShardBlock::Copy &b) { return a.entry < b.entry; });
+    std::sort(fp.begin(), fp.end(), [](const ShardBlock::Public &a, const ShardBlock::Public &b) { return a.placement != b.placement ? a.placement < b.placement : a.wire < b.wire; });
+    for (size_t k = 0; k < fa.size() && k < MAX_FINDINGS; k++) {
+        const SubcircuitInfo &info = in.infos->at(in.layout->id.at(fa[k].placement));
+        rep.arithmetic.first.push_back(ArithmeticFinding{(size_t)fa[k].placement, info.id, info.name, fa[k].first_row, fa[k].bad_rows, fa[k].u, fa[k].v, fa[k].w});
+    }
+    for (size_t k = 0; k < fc.size() && k < MAX_FINDINGS; k++) {
+        const EffectivePermutation &ep = *in.perm;
+        const uint64_t e = fc[k].entry;
+        rep.copy.first.push_back(CopyFinding{e, ep.dst.at(e) / (uint32_t)s_max, ep.dst.at(e) % (uint32_t)s_max, ep.x.at(e), ep.y.at(e), fc[k].value, fc[k].source});
+    }
+    for (size_t k = 0; k < fp.size() && k < MAX_FINDINGS; k++)
+        rep.pub.first.push_back(PublicFinding{(size_t)fp[k].index, (size_t)fp[k].placement, (size_t)fp[k].wire, fp[k].value, fp[k].instance});
+    rep.arithmetic.ok = rep.arithmetic.bad_cells == 0;
+    rep.copy.ok = rep.copy.bijection && rep.copy.bad_entries == 0;
+    rep.pub.ok = rep.pub.bad == 0;
+    return conclude(rep);
+}
 }  // namespace witness_check
 }  // namespace tkmk

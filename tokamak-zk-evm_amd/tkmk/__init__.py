@@ -99,7 +99,7 @@ SYMBOLS = [
     "tkmk_poly_div_by_vanishing_opt", "tkmk_poly_div_by_ruffini", "tkmk_r1cs_eval_rows",
     "tkmk_msm_multi_ex", "tkmk_msm_segmented", "tkmk_msm_segmented_status", "bls12_381_msm_convert_bases", "tkmk_r1cs_library_create", "tkmk_r1cs_library_destroy", "tkmk_r1cs_library_eval",
     "tkmk_r1cs_library_mix", "tkmk_fr_outer",
-    "tkmk_witness_route", "tkmk_fr_scatter_table", "tkmk_witness_check_r1cs", "tkmk_witness_check_copy", "tkmk_msm_set_pipeline_streams", "tkmk_msm_get_pipeline_streams", "tkmk_host_malloc", "tkmk_host_free", "tkmk_stats_reset", "tkmk_stats_get",
+    "tkmk_witness_route", "tkmk_fr_scatter_table", "tkmk_witness_check_r1cs", "tkmk_witness_check_copy", "tkmk_witness_check_copy_split", "tkmk_msm_set_pipeline_streams", "tkmk_msm_get_pipeline_streams", "tkmk_host_malloc", "tkmk_host_free", "tkmk_stats_reset", "tkmk_stats_get",
     "bls12_381_ntt_domain_size", "bn254_ntt_domain_size", "tkmk_poly_lincomb", "tkmk_bintt_padded", "tkmk_diag_device_switch", "tkmk_diag_gather_probe",
     "bls12_381_get_root_of_unity_with_generator", "tkmk_ntt_root_generator", "tkmk_ntt_set_root_generator", "tkmk_poly_geometric_grid", "tkmk_crs_identify_root", "tkmk_g1_check",
     "bls12_381_generate_random_affine_points", "bls12_381_generate_scalars", "bls12_381_polynomial_add", "bls12_381_polynomial_clone", "bls12_381_polynomial_coeffs_device_ptr", "bls12_381_polynomial_copy_coeffs", "bls12_381_polynomial_create_from_coefficients", "bls12_381_polynomial_create_from_rou_evaluations", "bls12_381_polynomial_degree", "bls12_381_polynomial_delete", "bls12_381_polynomial_divide", "bls12_381_polynomial_evaluate", "bls12_381_polynomial_get_coeff", "bls12_381_polynomial_multiply", "bls12_381_polynomial_multiply_by_scalar", "bls12_381_polynomial_nof_coeffs", "bls12_381_polynomial_slice", "bls12_381_polynomial_subtract", "bls12_381_vector_accumulate",
@@ -843,6 +843,8 @@ WITNESS_CHECK_ARGTYPES = {
                                 ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p],
     "tkmk_witness_check_copy": [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                 ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p],
+    "tkmk_witness_check_copy_split": [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64,
+                                      ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.c_void_p],
 }
 
 
@@ -877,6 +879,29 @@ def witness_check_copy(b, rows, cols, stride, dst_idx, src_x, src_y):
                                                          n, ctypes.byref(bad), ctypes.byref(first), None)
     if code not in (0, 11):
         raise TkmkError(code, "tkmk_witness_check_copy")
+    return bad.value, (None if first.value == (1 << 64) - 1 else first.value), code == 0
+
+
+def witness_check_copy_split(b_local, local_cells, dst_local, sources, n_sources, src_slot):
+    """tkmk_witness_check_copy_split, one rank's share of the copy comparison of a sharded prover: is b_local[dst_local[e]] =
+    sources[src_slot[e]] for every entry?  b_local / sources: DeviceBuffers of local_cells / n_sources plain Fr (this rank's cells; the
+    gathered source values); dst_local / src_slot: host index lists, or DeviceBuffers of uint32 (then n = their common length).
+    -> (bad_entries, first_bad_entry or None, in_range): in_range is False when some entry pointed outside one of the two buffers
+    (TKMK_ERR_INVALID_ARGUMENT: that entry was skipped, the others judged)"""
+    if hasattr(dst_local, "ptr"):
+        dev, n = [dst_local, src_slot], dst_local.nbytes // 4
+        assert src_slot.nbytes // 4 == n
+    else:
+        arrs = [np.ascontiguousarray(a, np.uint32) for a in (dst_local, src_slot)]
+        n = arrs[0].size
+        assert arrs[1].size == n
+        dev = [DeviceBuffer.from_host(a.view(np.uint8)) if n else None for a in arrs]
+    bad, first = ctypes.c_uint64(), ctypes.c_uint64()
+    ptr = lambda d: d.ptr if d is not None else None                                               # noqa: E731
+    code = _witness_check_fn("tkmk_witness_check_copy_split")(ptr(b_local), local_cells, ptr(dev[0]), ptr(sources), n_sources, ptr(dev[1]), n,
+                                                               ctypes.byref(bad), ctypes.byref(first), None)
+    if code not in (0, 11):
+        raise TkmkError(code, "tkmk_witness_check_copy_split")
     return bad.value, (None if first.value == (1 << 64) - 1 else first.value), code == 0
 
 

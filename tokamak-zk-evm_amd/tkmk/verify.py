@@ -21,6 +21,7 @@ def _lib(testing=False):
         l.tkmk_crs_audit_circuit_files.argtypes = l.tkmk_crs_audit_files.argtypes
         l.tkmk_witness_check_files.argtypes = [ctypes.c_char_p] * 2 + [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p)]
         l.tkmk_prover_check_witness.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p)]
+        l.tkmk_prover_check_witness_sharded.argtypes = l.tkmk_prover_check_witness.argtypes
         tail = [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p)]
         l.tkmk_verify_batch_files.argtypes = [ctypes.c_char_p] * 2 + [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32] + tail
         l.tkmk_prover_verify_batch.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t] + tail
@@ -151,19 +152,23 @@ def crs_audit(subcircuit_library_dir, crs_dir, testing=False, circuit=False):
     return ok.value == 1, _take_report(l, doc)
 
 
-def witness_check(subcircuit_library_dir, synthesizer_dir, prover=None, testing=False):
+def witness_check(subcircuit_library_dir, synthesizer_dir, prover=None, testing=False, collective=False):
     """-> (ok, report): does the witness of <synthesizer_dir> (placementVariables.json, permutation.json, instance.json) satisfy the circuit
     of <subcircuit_library_dir>, and if not, where?  tkmk_witness_check_files: a device, no reference string.  prover = an open
     service.Prover: tkmk_prover_check_witness against that context's library (subcircuit_library_dir is then not read; a sharded context
-    refuses with code 11).  report = {"ok", "reason", "arithmetic": {"ok", "placements", "bad_placements", "bad_cells", "first"}, "copy":
+    refuses with code 11).  collective=True (with prover): tkmk_prover_check_witness_sharded — EVERY rank of a sharded prover makes this
+    call with the same arguments (dist.run_ranks over the loopback transport) and gets the same verdict and report; on an unsharded
+    context it is the plain entry.  report = {"ok", "reason", "arithmetic": {"ok", "placements", "bad_placements", "bad_cells", "first"}, "copy":
     {"ok", "entries", "bijection", "bad_entries", "first"}, "public": {"ok", "wires", "bad", "first"}, "seconds"}: all three sections are
     always evaluated, `first` holds at most 8 findings each.  ok is what the verifier says about the proof made from the same documents.
     service.ProverError for an unreadable document (the message names the file) and without a device (code 12)."""
     l = _lib(prover.testing if prover is not None else testing)
     ok, doc = ctypes.c_int(-1), ctypes.c_void_p()
     if prover is not None:
-        name, testing = "tkmk_prover_check_witness", prover.testing
-        code = l.tkmk_prover_check_witness(prover._h, os.fsencode(synthesizer_dir), ctypes.byref(ok), ctypes.byref(doc))
+        name, testing = "tkmk_prover_check_witness_sharded" if collective else "tkmk_prover_check_witness", prover.testing
+        code = getattr(l, name)(prover._h, os.fsencode(synthesizer_dir), ctypes.byref(ok), ctypes.byref(doc))
+    elif collective:
+        raise ValueError("collective=True needs the prover whose ranks make the call")
     else:
         name = "tkmk_witness_check_files"
         code = l.tkmk_witness_check_files(os.fsencode(subcircuit_library_dir), os.fsencode(synthesizer_dir), ctypes.byref(ok), ctypes.byref(doc))
