@@ -5,6 +5,7 @@
 //   tkmk_witness_check_r1cs   u . v = w cell by cell over three rows x stride evaluation grids (the layout tkmk_r1cs_library_eval writes):
 //                             per column the count of failing rows and the smallest failing row
 //   tkmk_witness_check_copy   b[dst[e]] = b[X[e] * stride + Y[e]] entry by entry over the de-duplicated permutation arrays
+//   tkmk_witness_check_copy_split   the same comparison on one rank of a sharded prover: b_local[dst[e]] = sources[slot[e]]
 //
 // Both results are a count and a minimum over integers: they do not depend on the order the workgroups arrive in.  The field product is
 // Fr::mul of ff.h.
@@ -77,21 +78,21 @@ TK_API tkmk_error tkmk_witness_check_r1cs(const tkmk_fr *u_dev, const tkmk_fr *v
     return TKMK_SUCCESS;
 }
 
-// One lane per entry.  An entry whose destination or source lies outside the rows x cols cells of the stride-wide grid is never
-// dereferenced: it is counted in res[2] and takes no part in the verdict.  A wave's failing lanes are a ballot: their number is its
-// population count and the first of them its lowest set bit (lane order is entry order); the four waves of a workgroup meet in LDS and a
-// workgroup that saw a failure issues one atomicAdd and one atomicMin.   res: [0] bad entries, [1] first bad entry, [2] invalid entries
-__global__ __launch_bounds__(256) void k_witness_check_copy(const fr_t *__restrict__ b, uint32_t rows, uint32_t cols, uint32_t stride,
-                                                           const uint32_t *__restrict__ dst_idx, const uint32_t *__restrict__ src_x,
-                                                           const uint32_t *__restrict__ src_y, uint64_t n, unsigned long long *__restrict__ res) {
+// The copy comparison, one lane per entry.  WHICH two cells entry e compares is its caller's addressing (a functor: false when the entry
+// points outside its buffers — such an entry is never dereferenced, is counted in res[2] and takes no part in the verdict); everything
+// else is shared.  A wave's failing lanes are a ballot: their number is its population count and the first of them its lowest set bit
+// (lane order is entry order); the four waves of a workgroup meet in LDS and a workgroup that saw a failure issues one atomicAdd and one
+// atomicMin.   res: [0] bad entries, [1] first bad entry, [2] invalid entries
+template <class Cells>
+__global__ __launch_bounds__(256) void k_witness_check_copy(const Cells cells, uint64_t n, unsigned long long *__restrict__ res) {
     __shared__ unsigned long long s_bad[4], s_first[4], s_inv[4];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     bool bad = false, invalid = false;
     if (e < n) {
-        const uint32_t d = dst_idx[e], x = src_x[e], y = src_y[e];
-        if (d / stride >= rows || d % stride >= cols || x >= rows || y >= cols) invalid = true;
-        else bad = !Fr::eq(Fr::canon(tk_load(b + d)), Fr::canon(tk_load(b + (uint64_t)x * stride + y)));
+        const fr_t *value, *source;
+        if (!cells(e, value, source)) invalid = true;
+        else bad = !Fr::eq(Fr::canon(tk_load(value)), Fr::canon(tk_load(source)));
     }
     const unsigned long long m_bad = __ballot(bad), m_inv = __ballot(invalid);
     if (lane == 0) {
@@ -106,6 +107,52 @@ __global__ __launch_bounds__(256) void k_witness_check_copy(const fr_t *__restri
         if (nb) atomicAdd(res + 0, nb), atomicMin(res + 1, first);
         if (ni) atomicAdd(res + 2, ni);
     }
+}
+
+// b[dst[e]] against b[X[e] * stride + Y[e]] inside the rows x cols cells of one stride-wide grid
+struct CopyCellsGrid {
+    const fr_t *b;
+    uint32_t rows, cols, stride;
+    const uint32_t *dst_idx, *src_x, *src_y;
+    __device__ bool operator()(uint64_t e, const fr_t *&value, const fr_t *&source) const {
+        const uint32_t d = dst_idx[e], x = src_x[e], y = src_y[e];
+        if (d / stride >= rows || d % stride >= cols || x >= rows || y >= cols) return false;
+        value = b + d, source = b + (uint64_t)x * stride + y;
+        return true;
+    }
+};
+// One rank of a sharded prover: the destination cells are this rank's own (b_local, its columns of b), the source values arrive packed
+// from every rank in one gathered buffer (the copy section of host/tkmk_witness_check.hpp).  One 32-byte load from each buffer: the
+// destination indices ascend, the slots mostly do.
+struct CopyCellsSplit {
+    const fr_t *b_local, *sources;
+    uint64_t local_cells, n_sources;
+    const uint32_t *dst_local, *src_slot;
+    __device__ bool operator()(uint64_t e, const fr_t *&value, const fr_t *&source) const {
+        const uint32_t d = dst_local[e], s = src_slot[e];
+        if (d >= local_cells || s >= n_sources) return false;
+        value = b_local + d, source = sources + s;
+        return true;
+    }
+};
+
+// what both entries do once their arguments are checked: one workgroup per 256 entries, three counters down and up
+template <class Cells>
+static tkmk_error witness_check_copy_run(const Cells &cells, uint64_t n, uint64_t *bad_entries_out, uint64_t *first_bad_entry_out, tkmk_stream stream) {
+    TK_TRY(tk_require_device());
+    hipStream_t s = tk_stream(stream);
+    tk_frame frame(s);
+    tk_scratch d_res;
+    TK_TRY(d_res.alloc(3 * sizeof(unsigned long long), s));
+    const unsigned long long init[3] = {0ull, ~0ull, 0ull};
+    TK_HIP(hipMemcpyAsync(d_res.p, init, sizeof init, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_witness_check_copy<Cells>, tk_div_up(n, 256), 256, 0, s, cells, n, d_res.as<unsigned long long>());
+    TK_HIP(hipGetLastError());
+    unsigned long long res[3] = {0, 0, 0};
+    TK_HIP(hipMemcpyAsync(res, d_res.p, sizeof res, hipMemcpyDeviceToHost, s));
+    TK_HIP(hipStreamSynchronize(s));
+    *bad_entries_out = res[0], *first_bad_entry_out = res[1];
+    return res[2] ? TKMK_ERR_INVALID_ARGUMENT : TKMK_SUCCESS;
 }
 
 TK_API tkmk_error tkmk_witness_check_copy(const tkmk_fr *b_dev, uint32_t rows, uint32_t cols, uint32_t stride, const uint32_t *dst_idx_dev,
@@ -117,54 +164,8 @@ TK_API tkmk_error tkmk_witness_check_copy(const tkmk_fr *b_dev, uint32_t rows, u
     if (n_entries == 0) return TKMK_SUCCESS;
     if (!b_dev || !dst_idx_dev || !src_x_dev || !src_y_dev) return TKMK_ERR_INVALID_POINTER;
     if (stride == 0 || n_entries > (0x7FFFFFFFull << 8)) return TKMK_ERR_INVALID_ARGUMENT;   // one workgroup per 256 entries
-    TK_TRY(tk_require_device());
-    hipStream_t s = tk_stream(stream);
-    tk_frame frame(s);
-    tk_scratch d_res;
-    TK_TRY(d_res.alloc(3 * sizeof(unsigned long long), s));
-    const unsigned long long init[3] = {0ull, ~0ull, 0ull};
-    TK_HIP(hipMemcpyAsync(d_res.p, init, sizeof init, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_witness_check_copy, tk_div_up(n_entries, 256), 256, 0, s, (const fr_t *)b_dev, rows, cols, stride, dst_idx_dev, src_x_dev,
-                       src_y_dev, n_entries, d_res.as<unsigned long long>());
-    TK_HIP(hipGetLastError());
-    unsigned long long res[3] = {0, 0, 0};
-    TK_HIP(hipMemcpyAsync(res, d_res.p, sizeof res, hipMemcpyDeviceToHost, s));
-    TK_HIP(hipStreamSynchronize(s));
-    *bad_entries_out = res[0], *first_bad_entry_out = res[1];
-    return res[2] ? TKMK_ERR_INVALID_ARGUMENT : TKMK_SUCCESS;
-}
-
-// The copy comparison of one rank of a sharded prover: the destination cells are this rank's own (b_local, its columns of b), the source
-// values arrive packed from every rank in one gathered buffer (host/tkmk_witness_check.hpp run_sharded).  One lane per entry, one 32-byte
-// load from each buffer (the destination indices ascend, the slots mostly do); an entry whose destination or slot lies outside its
-// buffer is never dereferenced and counted in res[2].  The reduction is k_witness_check_copy's: ballot, LDS, one atomicAdd and one
-// atomicMin per workgroup that saw a failure.
-__global__ __launch_bounds__(256) void k_witness_check_copy_split(const fr_t *__restrict__ b_local, uint64_t local_cells,
-                                                                 const uint32_t *__restrict__ dst_local, const fr_t *__restrict__ sources,
-                                                                 uint64_t n_sources, const uint32_t *__restrict__ src_slot, uint64_t n,
-                                                                 unsigned long long *__restrict__ res) {
-    __shared__ unsigned long long s_bad[4], s_first[4], s_inv[4];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    bool bad = false, invalid = false;
-    if (e < n) {
-        const uint32_t d = dst_local[e], s = src_slot[e];
-        if (d >= local_cells || s >= n_sources) invalid = true;
-        else bad = !Fr::eq(Fr::canon(tk_load(b_local + d)), Fr::canon(tk_load(sources + s)));
-    }
-    const unsigned long long m_bad = __ballot(bad), m_inv = __ballot(invalid);
-    if (lane == 0) {
-        s_bad[wave] = (unsigned long long)__popcll(m_bad);
-        s_first[wave] = m_bad ? e + (unsigned long long)(__ffsll((long long)m_bad) - 1) : ~0ull;
-        s_inv[wave] = (unsigned long long)__popcll(m_inv);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long nb = 0, ni = 0, first = ~0ull;
-        for (int k = 0; k < 4; k++) nb += s_bad[k], ni += s_inv[k], first = s_first[k] < first ? s_first[k] : first;
-        if (nb) atomicAdd(res + 0, nb), atomicMin(res + 1, first);
-        if (ni) atomicAdd(res + 2, ni);
-    }
+    return witness_check_copy_run(CopyCellsGrid{(const fr_t *)b_dev, rows, cols, stride, dst_idx_dev, src_x_dev, src_y_dev}, n_entries, bad_entries_out,
+                                  first_bad_entry_out, stream);
 }
 
 TK_API tkmk_error tkmk_witness_check_copy_split(const tkmk_fr *b_local_dev, uint64_t local_cells, const uint32_t *dst_local_dev,
@@ -175,19 +176,6 @@ TK_API tkmk_error tkmk_witness_check_copy_split(const tkmk_fr *b_local_dev, uint
     if (n == 0) return TKMK_SUCCESS;
     if (!b_local_dev || !dst_local_dev || !sources_dev || !src_slot_dev) return TKMK_ERR_INVALID_POINTER;
     if (n > (0x7FFFFFFFull << 8)) return TKMK_ERR_INVALID_ARGUMENT;   // one workgroup per 256 entries
-    TK_TRY(tk_require_device());
-    hipStream_t s = tk_stream(stream);
-    tk_frame frame(s);
-    tk_scratch d_res;
-    TK_TRY(d_res.alloc(3 * sizeof(unsigned long long), s));
-    const unsigned long long init[3] = {0ull, ~0ull, 0ull};
-    TK_HIP(hipMemcpyAsync(d_res.p, init, sizeof init, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_witness_check_copy_split, tk_div_up(n, 256), 256, 0, s, (const fr_t *)b_local_dev, local_cells, dst_local_dev,
-                       (const fr_t *)sources_dev, n_sources, src_slot_dev, n, d_res.as<unsigned long long>());
-    TK_HIP(hipGetLastError());
-    unsigned long long res[3] = {0, 0, 0};
-    TK_HIP(hipMemcpyAsync(res, d_res.p, sizeof res, hipMemcpyDeviceToHost, s));
-    TK_HIP(hipStreamSynchronize(s));
-    *bad_entries_out = res[0], *first_bad_entry_out = res[1];
-    return res[2] ? TKMK_ERR_INVALID_ARGUMENT : TKMK_SUCCESS;
+    return witness_check_copy_run(CopyCellsSplit{(const fr_t *)b_local_dev, (const fr_t *)sources_dev, local_cells, n_sources, dst_local_dev, src_slot_dev}, n,
+                                  bad_entries_out, first_bad_entry_out, stream);
 }

@@ -46,6 +46,9 @@ static tkmk_error guarded(F &&fn) {
     } catch (const std::exception &e) {
         g_last_error = e.what();
         return TKMK_ERR_INVALID_ARGUMENT;
+    } catch (...) {   // nothing foreign crosses the C ABI
+        g_last_error = "unknown exception";
+        return TKMK_ERR_UNKNOWN;
     }
 }
 
@@ -151,11 +154,20 @@ TKP_API const char *tkmk_prover_last_error(void) { return g_last_error.c_str(); 
 TKP_API const char *tkmk_prover_crs_source(const tkmk_prover *p) { return p ? p->ctx->crs_source.c_str() : ""; }
 TKP_API uint32_t tkmk_prover_root_generator(const tkmk_prover *p) { return p ? p->ctx->root_generator : 0; }
 
-// ---- the verifier (host only: none of these touches the device, the default stream or a context's proving state) ----
-static void hand_over(bool verdict, const verify::Report &rep, int *ok, char **report_json_out) {
+// ---- entries that answer with a verdict and, where asked for, a report document: both cleared first, then written by hand_over ----
+template <class F>
+static tkmk_error verdict_entry(int *ok, char **report_json_out, F &&fn) {
+    *ok = 0;
+    if (report_json_out) *report_json_out = nullptr;
+    return guarded(fn);
+}
+template <class Report>
+static void hand_over(bool verdict, const Report &rep, int *ok, char **report_json_out) {
     if (report_json_out) *report_json_out = dup_string(rep.to_json());
     *ok = verdict ? 1 : 0;
 }
+
+// ---- the verifier (host only: none of these touches the device, the default stream or a context's proving state) ----
 
 TKP_API tkmk_error tkmk_pairing_product_is_one(const tkmk_g1_affine *p, const tkmk_g2_affine *q, size_t n, int *is_one) {
     if (!is_one || (n && (!p || !q))) return TKMK_ERR_INVALID_POINTER;
@@ -175,9 +187,7 @@ TKP_API tkmk_error tkmk_pairing_product_is_one(const tkmk_g1_affine *p, const tk
 TKP_API tkmk_error tkmk_verify_files(const char *subcircuit_library_dir, const char *crs_dir, const char *synthesizer_dir, const char *preprocess_dir,
                                      const char *proof_dir, uint32_t root_generator, int *ok, char **report_json_out) {
     if (!subcircuit_library_dir || !crs_dir || !synthesizer_dir || !preprocess_dir || !proof_dir || !ok) return TKMK_ERR_INVALID_POINTER;
-    *ok = 0;
-    if (report_json_out) *report_json_out = nullptr;
-    return guarded([&] {
+    return verdict_entry(ok, report_json_out, [&] {
         verify::Report rep;
         const bool verdict = verify::verify_files(subcircuit_library_dir, crs_dir, synthesizer_dir, preprocess_dir, proof_dir, root_generator, rep);
         hand_over(verdict, rep, ok, report_json_out);
@@ -187,16 +197,13 @@ TKP_API tkmk_error tkmk_verify_files(const char *subcircuit_library_dir, const c
 // the CRS audit (host/tkmk_crs_audit.hpp): device work on the default stream, so it takes the unsharded contexts' turn
 static tkmk_error crs_audit_entry(const char *entry, const char *subcircuit_library_dir, const char *crs_dir, bool circuit, int *ok, char **report_json_out) {
     if (!subcircuit_library_dir || !crs_dir || !ok) return TKMK_ERR_INVALID_POINTER;
-    *ok = 0;
-    if (report_json_out) *report_json_out = nullptr;
-    return guarded([&] {
+    return verdict_entry(ok, report_json_out, [&] {
         int ndev = 0;
         if (tkmk_device_count(&ndev) != TKMK_SUCCESS || ndev < 1) throw Error(TKMK_ERR_NO_DEVICE, std::string(entry) + ": no HIP device (the MI355X backend has no CPU fallback)");
         DefaultStreamTurn turn(false);
         crs_audit::Report rep;
         const bool verdict = crs_audit::audit_files(subcircuit_library_dir, crs_dir, rep, nullptr, circuit);
-        if (report_json_out) *report_json_out = dup_string(rep.to_json());
-        *ok = verdict ? 1 : 0;
+        hand_over(verdict, rep, ok, report_json_out);
     });
 }
 TKP_API tkmk_error tkmk_crs_audit_files(const char *subcircuit_library_dir, const char *crs_dir, int *ok, char **report_json_out) {
@@ -210,53 +217,42 @@ TKP_API tkmk_error tkmk_crs_audit_circuit_files(const char *subcircuit_library_d
 // the witness check (host/tkmk_witness_check.hpp; ProverContext::check_witness): device work on the default stream, like a proof
 TKP_API tkmk_error tkmk_witness_check_files(const char *subcircuit_library_dir, const char *synthesizer_dir, int *ok, char **report_json_out) {
     if (!subcircuit_library_dir || !synthesizer_dir || !ok) return TKMK_ERR_INVALID_POINTER;
-    *ok = 0;
-    if (report_json_out) *report_json_out = nullptr;
-    return guarded([&] {
+    return verdict_entry(ok, report_json_out, [&] {
         int ndev = 0;
         if (tkmk_device_count(&ndev) != TKMK_SUCCESS || ndev < 1) throw Error(TKMK_ERR_NO_DEVICE, "tkmk_witness_check_files: no HIP device (the MI355X backend has no CPU fallback)");
         DefaultStreamTurn turn(false);
         std::unique_ptr<ProverContext> ctx = ProverContext::open_circuit(subcircuit_library_dir);   // no reference string
         witness_check::Report rep;
         const bool verdict = ctx->check_witness(synthesizer_dir, rep);
-        if (report_json_out) *report_json_out = dup_string(rep.to_json());
-        *ok = verdict ? 1 : 0;
+        hand_over(verdict, rep, ok, report_json_out);
     });
 }
 TKP_API tkmk_error tkmk_prover_check_witness(tkmk_prover *p, const char *synthesizer_dir, int *ok, char **report_json_out) {
     if (!p || !synthesizer_dir || !ok) return TKMK_ERR_INVALID_POINTER;
-    *ok = 0;
-    if (report_json_out) *report_json_out = nullptr;
-    return guarded([&] {
+    return verdict_entry(ok, report_json_out, [&] {
         if (p->ctx->link)
             throw Error("tkmk_prover_check_witness: not available on a sharded context (the copy section crosses columns, and this entry is not collective: every rank calls tkmk_prover_check_witness_sharded instead)");
         DefaultStreamTurn turn(false);
         witness_check::Report rep;
         const bool verdict = p->ctx->check_witness(synthesizer_dir, rep);
-        if (report_json_out) *report_json_out = dup_string(rep.to_json());
-        *ok = verdict ? 1 : 0;
+        hand_over(verdict, rep, ok, report_json_out);
     });
 }
 // collective: every rank of a sharded context, with the same arguments (ProverContext::check_witness_sharded)
 TKP_API tkmk_error tkmk_prover_check_witness_sharded(tkmk_prover *p, const char *synthesizer_dir, int *ok, char **report_json_out) {
     if (!p || !synthesizer_dir || !ok) return TKMK_ERR_INVALID_POINTER;
-    *ok = 0;
-    if (report_json_out) *report_json_out = nullptr;
-    return guarded([&] {
+    return verdict_entry(ok, report_json_out, [&] {
         DefaultStreamTurn turn((bool)p->ctx->link);
         witness_check::Report rep;
         const bool verdict = p->ctx->check_witness_sharded(synthesizer_dir, rep);
-        if (report_json_out) *report_json_out = dup_string(rep.to_json());
-        *ok = verdict ? 1 : 0;
+        hand_over(verdict, rep, ok, report_json_out);
     });
 }
 
 TKP_API tkmk_error tkmk_prover_verify(tkmk_prover *p, const char *synthesizer_dir, const char *preprocess_dir, const char *proof_dir, int *ok,
                                       char **report_json_out) {
     if (!p || !synthesizer_dir || !preprocess_dir || !proof_dir || !ok) return TKMK_ERR_INVALID_POINTER;
-    *ok = 0;
-    if (report_json_out) *report_json_out = nullptr;
-    return guarded([&] {
+    return verdict_entry(ok, report_json_out, [&] {
         const ProverContext &c = *p->ctx;
         verify::Inputs in;
         in.sp.n = c.sp.n, in.sp.l = c.sp.l, in.sp.l_D = c.sp.l_D, in.sp.s_max = c.sp.s_max, in.sp.l_user = c.sp.l_user, in.sp.l_free = c.sp.l_free;

@@ -516,17 +516,16 @@ class ProverContext {
         }
         // the three sections of host/tkmk_witness_check.hpp over what the steps above have built; u / v / w: the grids, wherever the caller
         // keeps them by now.  Sharded (world > 1): collective — this rank's columns, one device and one host all-gather, the same report on
-        // every rank (witness_check::run_sharded).
+        // every rank (witness_check::run).
         bool run_check(const ScalarField *u_dev, const ScalarField *v_dev, const ScalarField *w_dev, const ScalarField *b_dev, witness_check::Report &rep) const {
             witness_check::Inputs in;
             in.sp = &c.sp, in.infos = &c.infos, in.layout = &W, in.staged = c.pinned_;
             in.u = u_dev, in.v = v_dev, in.w = w_dev, in.b = b_dev;
-            in.perm = &perm, in.d_dst = d_dst.ptr(), in.d_x = d_x.ptr(), in.d_y = d_y.ptr();
+            in.perm = &perm, in.local_entry = sh.world > 1 ? &local_entry : nullptr, in.local_dst = &dst();   // one rank: every entry, in place
+            in.d_dst = d_dst.ptr(), in.d_x = d_x.ptr(), in.d_y = d_y.ptr();
             in.a_pub_user = &a_pub_user, in.a_pub_block = &a_pub_block, in.a_pub_function = &a_pub_function;
-            if (sh.world == 1) return witness_check::run(in, rep);
-            witness_check::ShardInputs si;
-            si.link = &c.link, si.lc = lc, si.placements = PL, si.local_entry = &local_entry, si.local_dst = &local_dst;
-            return witness_check::run_sharded(in, si, rep);
+            in.shard = sh, in.link = &c.link, in.lc = lc, in.placements = PL;
+            return witness_check::run(in, rep);
         }
 
       private:

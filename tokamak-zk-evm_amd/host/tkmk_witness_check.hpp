@@ -3,8 +3,8 @@
 //   arithmetic   u . v = w in every cell of the n x s_max evaluation grids (tkmk_witness_check_r1cs): a placement whose variables do not
 //                satisfy its subcircuit's R1CS is named with its first failing row
 //   copy         b[row][col] = b[X][Y] for every entry of the EFFECTIVE permutation — the arrays after init's last-writer de-duplication
-//                (tkmk_witness_check_copy) — and that map, extended by the identity on the cells no entry writes, is a bijection of
-//                the m_I x s_max cells (host, over the bitmap of destinations)
+//                — and that map, extended by the identity on the cells no entry writes, is a bijection of the m_I x s_max cells (host, over
+//                the bitmap of destinations)
 //   public       every public wire of the four buffer placements equals the instance.json value at its flattenMap index (host: a few
 //                hundred values that are already in the staging buffer)
 // The reference has these diagnostics behind its `testing-mode` feature, as host loops over downloaded evaluations (prove/src/lib.rs:916-1017
@@ -12,18 +12,21 @@
 // refuses: `ok` here equals tkmk_prover_verify's verdict on the proof the unguarded prover makes from the same documents
 // (tests/test_gpu_witness_check.py).
 //
-// One proof over G ranks (run_sharded; ProverContext::check_witness_sharded and the knob inside a sharded init): a rank holds the columns
-// c = rank mod G of u, v, w, b, so arithmetic and public are local — a placement is a column, and only its owner staged its values — while
-// a copy entry ties cell (row, col) on rank col mod G to cell (X, Y) on rank Y mod G.  Every rank knows the whole effective permutation,
-// so every rank knows, without a message, the list S_s of entries whose source lives on rank s (entry order).  Rank s packs those values
-// of its b (tkmk_gather_rows_device), ONE tkmk_comm_all_gather_dev of max_s |S_s| values per rank gives every rank all of them, and each
-// rank compares its own destination cells against its slots of the gathered buffer (tkmk_witness_check_copy_split).  A rank receives
-// G * max_s |S_s| * 32 bytes.  The destinations are distinct, so the sum of the |S_s| is at most the number of cells: evenly spread sources
-// make the payload at most one copy of b (m_I * s_max * 32 bytes, 128 MB at BASELINE.json configs[3]); the padding to the longest list
-// costs more when the sources crowd onto few ranks.  Then ONE tkmk_comm_all_gather_host carries a fixed-size block per rank (counters, at most
-// MAX_FINDINGS findings per section, an error text) and every rank merges all blocks into the same report: totals summed, findings in the
-// order the unsharded code enumerates them (placement; entry; placement, wire), cut to MAX_FINDINGS.  An input error only one rank can
-// see (the public wires of placement 2 exist on its owner alone) travels in the block and is every rank's error, with one text.
+// One code path for one rank and for G (run): rank r holds the columns c = r mod G of u, v, w, b — all of them when G = 1.  Each section
+// writes what this rank found into a ShardBlock (counters, at most MAX_FINDINGS findings per section, an error text), and merge() makes the
+// report from the blocks of all ranks: totals summed, findings in the order placement; entry; placement, wire, cut to MAX_FINDINGS.  With
+// G = 1 the one block is merged as it stands and nothing is exchanged.  With G > 1 (collective: ProverContext::check_witness_sharded and
+// the knob inside a sharded init) ONE tkmk_comm_all_gather_host carries the blocks, and every rank merges them into the same report.
+//   arithmetic, public   local: a placement is a column, and only its owner staged its values.  An input error only one rank can see (the
+//                public wires of placement 2 exist on its owner alone) travels in the block and is every rank's error, with one text.
+//   copy         an entry ties cell (row, col) on rank col mod G to cell (X, Y) on rank Y mod G.  G = 1: tkmk_witness_check_copy over b.
+//                G > 1: every rank knows the whole effective permutation, so every rank knows, without a message, the list S_s of entries
+//                whose source lives on rank s (entry order).  Rank s packs those values of its b (tkmk_gather_rows_device), ONE
+//                tkmk_comm_all_gather_dev of max_s |S_s| values per rank gives every rank all of them, and each rank compares its own
+//                destination cells against its slots of the gathered buffer (tkmk_witness_check_copy_split).  A rank receives
+//                G * max_s |S_s| * 32 bytes.  The destinations are distinct, so the sum of the |S_s| is at most the number of cells: evenly
+//                spread sources make the payload at most one copy of b (m_I * s_max * 32 bytes, 128 MB at BASELINE.json configs[3]); the
+//                padding to the longest list costs more when the sources crowd onto few ranks.
 //
 // Not covered: a sharded bin/witness-check / tkmk_witness_check_files (there is no sharded context without a reference string), BN254,
 // WHICH variable of a failing row is wrong, and an all-to-all in place of the all-gather (a rank needs only the sources of its own
@@ -186,142 +189,23 @@ struct Report {
     }
 };
 
-// What the three sections read.  Device pointers are borrowed; everything is the unsharded form (element (row, col) at row * s_max + col).
+// What the three sections read on rank shard.rank of shard.world.  Device pointers are borrowed and are this rank's columns: u, v, w
+// (n x lc) and b (m_I x lc), element (row, local column k) at row * lc + k; local column k is global column rank + k G.  One rank: lc =
+// s_max, every placement and every entry is this rank's, the local destinations are perm's own.
 struct Inputs {
     const SetupParams *sp = nullptr;
     const std::vector<SubcircuitInfo> *infos = nullptr;
     const WitnessLayout *layout = nullptr;      // kind and first staged value of every placement
     const ScalarField *staged = nullptr;        // the parsed witness on the host (the pinned staging buffer)
-    const ScalarField *u = nullptr, *v = nullptr, *w = nullptr, *b = nullptr;             // n x s_max (u, v, w) and m_I x s_max (b) on the device
-    const EffectivePermutation *perm = nullptr;
-    const uint32_t *d_dst = nullptr, *d_x = nullptr, *d_y = nullptr;                      // perm's three arrays on the device (null when it is empty)
+    const ScalarField *u = nullptr, *v = nullptr, *w = nullptr, *b = nullptr;
+    const EffectivePermutation *perm = nullptr;           // the replicated whole, global indices
+    const std::vector<uint32_t> *local_entry = nullptr;   // this rank's entries: index into perm's arrays, ascending; null: all of them
+    const std::vector<uint32_t> *local_dst = nullptr;     // ... and their destinations row * lc + col / G
+    const uint32_t *d_dst = nullptr, *d_x = nullptr, *d_y = nullptr;   // local_dst and its sources X, Y on the device (null when empty; X, Y are read by one rank only)
     const std::vector<ScalarField> *a_pub_user = nullptr, *a_pub_block = nullptr, *a_pub_function = nullptr;
-};
-
-inline void check_arithmetic(const Inputs &in, Report &rep) {
-    const size_t s_max = in.sp->s_max, n = in.sp->n, P = in.layout->id.size();
-    auto &sec = rep.arithmetic;
-    sec.placements = P;
-    if (P) {
-        DeviceVec<uint32_t> d_cnt(P), d_first(P);
-        check(tkmk_witness_check_r1cs(in.u, in.v, in.w, (uint32_t)n, (uint32_t)P, (uint32_t)s_max, d_cnt.ptr(), d_first.ptr(), &sec.bad_cells, nullptr), "tkmk_witness_check_r1cs");
-        if (sec.bad_cells) {
-            std::vector<uint32_t> cnt(P), first(P);
-            d_cnt.copy_to_host(cnt.data(), P), d_first.copy_to_host(first.data(), P);
-            for (size_t q = 0; q < P; q++) {
-                if (!cnt[q]) continue;
-                sec.bad_placements++;
-                if (sec.first.size() >= MAX_FINDINGS) continue;
-                const SubcircuitInfo &info = in.infos->at(in.layout->id[q]);
-                ArithmeticFinding f{q, info.id, info.name, first[q], cnt[q], {}, {}, {}};
-                const size_t at = (size_t)first[q] * s_max + q;
-                check(tkmk_memcpy_d2h(&f.u, in.u + at, sizeof(ScalarField)), "memcpy_d2h");
-                check(tkmk_memcpy_d2h(&f.v, in.v + at, sizeof(ScalarField)), "memcpy_d2h");
-                check(tkmk_memcpy_d2h(&f.w, in.w + at, sizeof(ScalarField)), "memcpy_d2h");
-                sec.first.push_back(std::move(f));
-            }
-        }
-    }
-    sec.ok = sec.bad_cells == 0;
-}
-
-inline void check_copy(const Inputs &in, Report &rep) {
-    const size_t s_max = in.sp->s_max, m_i = in.sp->m_i();
-    const EffectivePermutation &ep = *in.perm;
-    auto &sec = rep.copy;
-    sec.entries = ep.dst.size();
-    uint32_t twice = 0;
-    sec.bijection = is_bijection(ep, s_max, &twice);
-    sec.twice_row = twice / (uint32_t)s_max, sec.twice_col = twice % (uint32_t)s_max;
-    // the first MAX_FINDINGS failing entries: the kernel names the first one of a range, so the next search starts behind it
-    uint64_t from = 0;
-    while (from < sec.entries) {
-        uint64_t bad = 0, first = UINT64_MAX;
-        check(tkmk_witness_check_copy(in.b, (uint32_t)m_i, (uint32_t)s_max, (uint32_t)s_max, in.d_dst + from, in.d_x + from, in.d_y + from, sec.entries - from, &bad, &first, nullptr),
-              "tkmk_witness_check_copy");
-        if (from == 0) sec.bad_entries = bad;
-        if (!bad || sec.first.size() >= MAX_FINDINGS) break;
-        const uint64_t e = from + first;
-        CopyFinding f{e, ep.dst[e] / (uint32_t)s_max, ep.dst[e] % (uint32_t)s_max, ep.x[e], ep.y[e], {}, {}};
-        check(tkmk_memcpy_d2h(&f.value, in.b + ep.dst[e], sizeof(ScalarField)), "memcpy_d2h");
-        check(tkmk_memcpy_d2h(&f.source, in.b + (size_t)f.X * s_max + f.Y, sizeof(ScalarField)), "memcpy_d2h");
-        sec.first.push_back(f);
-        from = e + 1;
-    }
-    sec.ok = sec.bijection && sec.bad_entries == 0;
-}
-
-// the public wires of the four buffer placements (encode_O_pub_free / encode_O_pub_fix, libs/src/group_structures/mod.rs:145-229: the outputs
-// of bufferPubOut, the inputs of bufferPubIn / bufferBlockIn / bufferEVMIn) against a_pub_user ++ a_pub_block ++ a_pub_function
-// (first, step): the placements q = first, first + step, ... — all of them, or those of one rank of a sharded prover
-inline void check_public(const Inputs &in, Report &rep, size_t first = 0, size_t step = 1) {
-    const SetupParams &sp = *in.sp;
-    auto &sec = rep.pub;
-    const size_t P = std::min<size_t>(4, in.layout->id.size());
-    for (size_t q = first; q < P; q += step) {
-        const SubcircuitInfo &info = in.infos->at(in.layout->id[q]);
-        const std::array<size_t, 2> *rng = nullptr;
-        if (info.name == "bufferPubOut") rng = &info.Out_idx;
-        else if (info.name == "bufferPubIn" || info.name == "bufferBlockIn" || info.name == "bufferEVMIn") rng = &info.In_idx;
-        if (!rng) continue;
-        for (size_t j = (*rng)[0]; j < (*rng)[0] + (*rng)[1]; j++) {
-            if (j >= info.Nwires) throw Error("subcircuitInfo.json: public wire range outside the subcircuit");
-            const size_t g = info.flattenMap[j];
-            if (g >= sp.l) throw Error("subcircuitInfo.json: public wire mapped outside [0, l)");
-            const std::vector<ScalarField> &src = g < sp.l_user ? *in.a_pub_user : g < sp.l_free ? *in.a_pub_block : *in.a_pub_function;
-            const size_t at = g < sp.l_user ? g : g < sp.l_free ? g - sp.l_user : g - sp.l_free;
-            if (at >= src.size()) throw Error("instance.json: no value for public wire " + std::to_string(g));
-            const ScalarField &val = in.staged[in.layout->off[q] + j];
-            sec.wires++;
-            if (fr_eq(val, src[at])) continue;
-            sec.bad++;
-            if (sec.first.size() < MAX_FINDINGS) sec.first.push_back(PublicFinding{g, q, j, val, src[at]});
-        }
-    }
-    sec.ok = sec.bad == 0;
-}
-
-// the verdict and `reason` from the three sections' findings
-inline bool conclude(Report &rep) {
-    rep.ok = rep.arithmetic.ok && rep.copy.ok && rep.pub.ok;
-    rep.reason.clear();
-    if (!rep.arithmetic.ok) {
-        const ArithmeticFinding &f = rep.arithmetic.first.front();
-        rep.reason = "arithmetic: placement " + std::to_string(f.placement) + " (subcircuit " + std::to_string(f.subcircuit_id) + ", " + f.name +
-                     ") does not satisfy its R1CS: " + std::to_string(f.bad_rows) + " failing row(s), the first is row " + std::to_string(f.first_row);
-    } else if (!rep.copy.ok) {
-        if (!rep.copy.bijection)
-            rep.reason = "copy: the permutation is not a bijection: cell (row " + std::to_string(rep.copy.twice_row) + ", col " + std::to_string(rep.copy.twice_col) +
-                         ") is the image of two cells";
-        else {
-            const CopyFinding &f = rep.copy.first.front();
-            rep.reason = "copy: entry " + std::to_string(f.entry) + " (row " + std::to_string(f.row) + ", col " + std::to_string(f.col) + ") differs from its source (X " +
-                         std::to_string(f.X) + ", Y " + std::to_string(f.Y) + "): " + std::to_string(rep.copy.bad_entries) + " failing entries";
-        }
-    } else if (!rep.pub.ok) {
-        const PublicFinding &f = rep.pub.first.front();
-        rep.reason = "public: wire " + std::to_string(f.wire) + " of placement " + std::to_string(f.placement) + " differs from instance.json at public index " +
-                     std::to_string(f.index) + ": " + std::to_string(rep.pub.bad) + " mismatch(es)";
-    }
-    return rep.ok;
-}
-
-inline bool run(const Inputs &in, Report &rep) {
-    check_arithmetic(in, rep);
-    check_copy(in, rep);
-    check_public(in, rep);
-    return conclude(rep);
-}
-
-// ---- one proof over G ranks (see the head of this file) ----
-// What a rank of a sharded prover adds to Inputs, whose device pointers are then this rank's columns (u, v, w: n x lc, b: m_I x lc, element
-// (row, local column k) at row * lc + k; local column k is global column rank + k G), whose `perm` is the replicated whole and whose
-// d_dst holds the local destinations; d_x / d_y are not read.
-struct ShardInputs {
-    const ShardLink *link = nullptr;
-    size_t lc = 0, placements = 0;                         // this rank's columns of s_max, and its placements (the first `placements` columns)
-    const std::vector<uint32_t> *local_entry = nullptr;    // this rank's entries: index into perm's arrays, ascending ...
-    const std::vector<uint32_t> *local_dst = nullptr;      // ... and their destinations row * lc + col / G
+    Shard shard;
+    const ShardLink *link = nullptr;            // the communicator of shard.world > 1; not used by one rank
+    size_t lc = 0, placements = 0;              // this rank's columns of s_max, and its placements (the first `placements` columns)
 };
 
 // the block a rank contributes to the merge: plain data of one size on every rank
@@ -351,11 +235,11 @@ struct ShardBlock {
 static_assert(std::is_trivially_copyable<ShardBlock>::value, "ShardBlock travels as bytes");
 
 // this rank's columns of the arithmetic section: local column k is placement rank + k G
-inline void shard_arithmetic(const Inputs &in, const ShardInputs &sh, ShardBlock &blk) {
-    const size_t n = in.sp->n, PL = sh.placements, G = sh.link->shard.world, rank = sh.link->shard.rank;
+inline void arithmetic_section(const Inputs &in, ShardBlock &blk) {
+    const size_t n = in.sp->n, PL = in.placements, G = in.shard.world, rank = in.shard.rank;
     if (!PL) return;
     DeviceVec<uint32_t> d_cnt(PL), d_first(PL);
-    check(tkmk_witness_check_r1cs(in.u, in.v, in.w, (uint32_t)n, (uint32_t)PL, (uint32_t)sh.lc, d_cnt.ptr(), d_first.ptr(), &blk.bad_cells, nullptr), "tkmk_witness_check_r1cs");
+    check(tkmk_witness_check_r1cs(in.u, in.v, in.w, (uint32_t)n, (uint32_t)PL, (uint32_t)in.lc, d_cnt.ptr(), d_first.ptr(), &blk.bad_cells, nullptr), "tkmk_witness_check_r1cs");
     if (!blk.bad_cells) return;
     std::vector<uint32_t> cnt(PL), first(PL);
     d_cnt.copy_to_host(cnt.data(), PL), d_first.copy_to_host(first.data(), PL);
@@ -365,18 +249,49 @@ inline void shard_arithmetic(const Inputs &in, const ShardInputs &sh, ShardBlock
         if (blk.n_arithmetic >= MAX_FINDINGS) continue;
         ShardBlock::Arithmetic &f = blk.arithmetic[blk.n_arithmetic++];
         f.placement = rank + k * G, f.first_row = first[k], f.bad_rows = cnt[k];
-        const size_t at = (size_t)first[k] * sh.lc + k;
+        const size_t at = (size_t)first[k] * in.lc + k;
         check(tkmk_memcpy_d2h(&f.u, in.u + at, sizeof(ScalarField)), "memcpy_d2h");
         check(tkmk_memcpy_d2h(&f.v, in.v + at, sizeof(ScalarField)), "memcpy_d2h");
         check(tkmk_memcpy_d2h(&f.w, in.w + at, sizeof(ScalarField)), "memcpy_d2h");
     }
 }
 
-// the values of the copy section: the one device all-gather, then this rank's entries against the gathered sources
-inline void shard_copy_values(const Inputs &in, const ShardInputs &sh, ShardBlock &blk) {
-    const size_t m_i = in.sp->m_i(), G = sh.link->shard.world, rank = sh.link->shard.rank, lc = sh.lc;
+// The first MAX_FINDINGS failing ones of this rank's n entries (the local lists ascend in the global entry index).  compare(from, &bad,
+// &first) counts the failing entries of [from, n) and names the first of them relative to `from`, so the next search starts behind it;
+// source_of(k) is where entry k's source value lies on the device.
+template <class Compare, class SourceOf>
+inline void copy_walk(const Inputs &in, uint64_t n, ShardBlock &blk, Compare compare, SourceOf source_of) {
+    uint64_t from = 0;
+    while (from < n) {
+        uint64_t bad = 0, first = UINT64_MAX;
+        compare(from, &bad, &first);
+        if (from == 0) blk.bad_entries = bad;
+        if (!bad || blk.n_copy >= MAX_FINDINGS) break;
+        const uint64_t k = from + first;
+        ShardBlock::Copy &f = blk.copy[blk.n_copy++];
+        f.entry = in.local_entry ? (*in.local_entry)[k] : k;
+        check(tkmk_memcpy_d2h(&f.value, in.b + (*in.local_dst)[k], sizeof(ScalarField)), "memcpy_d2h");
+        check(tkmk_memcpy_d2h(&f.source, source_of(k), sizeof(ScalarField)), "memcpy_d2h");
+        from = k + 1;
+    }
+}
+
+// the values of the copy section.  One rank: the entries against b itself.  G ranks: the one device all-gather, then this rank's entries
+// against the gathered sources
+inline void copy_section(const Inputs &in, ShardBlock &blk) {
+    const size_t s_max = in.sp->s_max, m_i = in.sp->m_i(), G = in.shard.world, rank = in.shard.rank, lc = in.lc;
     const EffectivePermutation &ep = *in.perm;
     const size_t E = ep.dst.size();
+    if (G == 1) {
+        copy_walk(
+            in, E, blk,
+            [&](uint64_t from, uint64_t *bad, uint64_t *first) {
+                check(tkmk_witness_check_copy(in.b, (uint32_t)m_i, (uint32_t)s_max, (uint32_t)s_max, in.d_dst + from, in.d_x + from, in.d_y + from, E - from, bad, first, nullptr),
+                      "tkmk_witness_check_copy");
+            },
+            [&](uint64_t e) { return in.b + (size_t)ep.x[e] * s_max + ep.y[e]; });
+        return;
+    }
     // S_s, from the replicated arrays alone: entry e is number pos[e] of the entries whose source column Y lives on rank Y mod G
     std::vector<uint32_t> pos(E), count(G, 0), mine;
     for (size_t e = 0; e < E; e++) {
@@ -394,68 +309,101 @@ inline void shard_copy_values(const Inputs &in, const ShardInputs &sh, ShardBloc
         check(tkmk_gather_rows_device(in.b, sizeof(ScalarField), d_mine.ptr(), mine.size(), send.ptr(), nullptr), "tkmk_gather_rows_device");
         check(tkmk_device_synchronize(), "synchronize");   // d_mine goes here
     }
-    check(sh.link->all_gather_dev(sh.link->comm, send.ptr(), pad * sizeof(ScalarField), sources.ptr()), "tkmk_comm_all_gather_dev");
-    const std::vector<uint32_t> &entry = *sh.local_entry, &dst = *sh.local_dst;
+    check(in.link->all_gather_dev(in.link->comm, send.ptr(), pad * sizeof(ScalarField), sources.ptr()), "tkmk_comm_all_gather_dev");
+    const std::vector<uint32_t> &entry = *in.local_entry;
     const size_t n = entry.size();
     if (!n) return;
     std::vector<uint32_t> slot(n);
     for (size_t k = 0; k < n; k++) slot[k] = (ep.y[entry[k]] % (uint32_t)G) * (uint32_t)pad + pos[entry[k]];
     DeviceVec<uint32_t> d_slot = DeviceVec<uint32_t>::from_host(slot);
-    // the first MAX_FINDINGS failing entries of this rank, as check_copy finds them: the local lists ascend in the global entry index
-    uint64_t from = 0;
-    while (from < n) {
-        uint64_t bad = 0, first = UINT64_MAX;
-        check(tkmk_witness_check_copy_split(in.b, m_i * lc, in.d_dst + from, sources.ptr(), G * pad, d_slot.ptr() + from, n - from, &bad, &first, nullptr),
-              "tkmk_witness_check_copy_split");
-        if (from == 0) blk.bad_entries = bad;
-        if (!bad || blk.n_copy >= MAX_FINDINGS) break;
-        const uint64_t k = from + first;
-        ShardBlock::Copy &f = blk.copy[blk.n_copy++];
-        f.entry = entry[k];
-        check(tkmk_memcpy_d2h(&f.value, in.b + dst[k], sizeof(ScalarField)), "memcpy_d2h");
-        check(tkmk_memcpy_d2h(&f.source, sources.ptr() + slot[k], sizeof(ScalarField)), "memcpy_d2h");
-        from = k + 1;
+    copy_walk(
+        in, n, blk,
+        [&](uint64_t from, uint64_t *bad, uint64_t *first) {
+            check(tkmk_witness_check_copy_split(in.b, m_i * lc, in.d_dst + from, sources.ptr(), G * pad, d_slot.ptr() + from, n - from, bad, first, nullptr),
+                  "tkmk_witness_check_copy_split");
+        },
+        [&](uint64_t k) { return sources.ptr() + slot[k]; });
+}
+
+// the public wires of the four buffer placements (encode_O_pub_free / encode_O_pub_fix, libs/src/group_structures/mod.rs:145-229: the outputs
+// of bufferPubOut, the inputs of bufferPubIn / bufferBlockIn / bufferEVMIn) against a_pub_user ++ a_pub_block ++ a_pub_function
+// — those of placement q, which the rank that staged its values checks
+inline void check_public(const Inputs &in, ShardBlock &blk, size_t q) {
+    const SetupParams &sp = *in.sp;
+    if (q >= in.layout->id.size()) return;
+    const SubcircuitInfo &info = in.infos->at(in.layout->id[q]);
+    const std::array<size_t, 2> *rng = nullptr;
+    if (info.name == "bufferPubOut") rng = &info.Out_idx;
+    else if (info.name == "bufferPubIn" || info.name == "bufferBlockIn" || info.name == "bufferEVMIn") rng = &info.In_idx;
+    if (!rng) return;
+    for (size_t j = (*rng)[0]; j < (*rng)[0] + (*rng)[1]; j++) {
+        if (j >= info.Nwires) throw Error("subcircuitInfo.json: public wire range outside the subcircuit");
+        const size_t g = info.flattenMap[j];
+        if (g >= sp.l) throw Error("subcircuitInfo.json: public wire mapped outside [0, l)");
+        const std::vector<ScalarField> &src = g < sp.l_user ? *in.a_pub_user : g < sp.l_free ? *in.a_pub_block : *in.a_pub_function;
+        const size_t at = g < sp.l_user ? g : g < sp.l_free ? g - sp.l_user : g - sp.l_free;
+        if (at >= src.size()) throw Error("instance.json: no value for public wire " + std::to_string(g));
+        const ScalarField &val = in.staged[in.layout->off[q] + j];
+        blk.wires++;
+        if (fr_eq(val, src[at])) continue;
+        blk.bad_public++;
+        if (blk.n_public < MAX_FINDINGS) blk.pub[blk.n_public++] = ShardBlock::Public{g, q, j, val, src[at]};
     }
 }
 
-// The three sections on rank link->shard.rank of G > 1; collective: every rank calls it, every rank gets the same report and verdict.
-// Exchanges: one tkmk_comm_all_gather_dev (none when the permutation is empty) and one tkmk_comm_all_gather_host.  A device or transport
-// failure leaves as an exception with the peers possibly waiting: the caller aborts the communicator (ProverContext does).
-inline bool run_sharded(const Inputs &in, const ShardInputs &sh, Report &rep) {
-    const size_t s_max = in.sp->s_max, G = sh.link->shard.world, rank = sh.link->shard.rank;
-    ShardBlock blk;
-    std::memset(&blk, 0, sizeof blk);
-    shard_arithmetic(in, sh, blk);
-    shard_copy_values(in, sh, blk);
-    {
-        Report own;   // placement q < 4 is checked by rank q mod G, the only one that staged its values; one placement per call
-        for (size_t q = rank; q < 4 && !blk.failed; q += G) {
-            try {
-                check_public(in, own, q, 4);
-            } catch (const Error &e) {
-                if (e.code != TKMK_ERR_INVALID_ARGUMENT) throw;
-                blk.failed = 1, blk.failed_placement = (uint32_t)q;
-                snprintf(blk.error, sizeof blk.error, "%s", e.what());
-            }
+// the verdict and `reason` from the three sections' findings
+inline bool conclude(Report &rep) {
+    rep.ok = rep.arithmetic.ok && rep.copy.ok && rep.pub.ok;
+    rep.reason.clear();
+    if (!rep.arithmetic.ok) {
+        const ArithmeticFinding &f = rep.arithmetic.first.front();
+        rep.reason = "arithmetic: placement " + std::to_string(f.placement) + " (subcircuit " + std::to_string(f.subcircuit_id) + ", " + f.name +
+                     ") does not satisfy its R1CS: " + std::to_string(f.bad_rows) + " failing row(s), the first is row " + std::to_string(f.first_row);
+    } else if (!rep.copy.ok) {
+        if (!rep.copy.bijection)
+            rep.reason = "copy: the permutation is not a bijection: cell (row " + std::to_string(rep.copy.twice_row) + ", col " + std::to_string(rep.copy.twice_col) +
+                         ") is the image of two cells";
+        else {
+            const CopyFinding &f = rep.copy.first.front();
+            rep.reason = "copy: entry " + std::to_string(f.entry) + " (row " + std::to_string(f.row) + ", col " + std::to_string(f.col) + ") differs from its source (X " +
+                         std::to_string(f.X) + ", Y " + std::to_string(f.Y) + "): " + std::to_string(rep.copy.bad_entries) + " failing entries";
         }
-        blk.wires = own.pub.wires, blk.bad_public = own.pub.bad, blk.n_public = own.pub.first.size();
-        for (size_t k = 0; k < own.pub.first.size(); k++) {
-            const PublicFinding &f = own.pub.first[k];
-            blk.pub[k] = ShardBlock::Public{f.index, f.placement, f.wire, f.value, f.instance};
+    } else if (!rep.pub.ok) {
+        const PublicFinding &f = rep.pub.first.front();
+        rep.reason = "public: wire " + std::to_string(f.wire) + " of placement " + std::to_string(f.placement) + " differs from instance.json at public index " +
+                     std::to_string(f.index) + ": " + std::to_string(rep.pub.bad) + " mismatch(es)";
+    }
+    return rep.ok;
+}
+
+// this rank's share of the public section: placement q < 4 is checked by rank q mod G, the only one that staged its values.  G ranks: an
+// input error is carried in the block (merge makes it every rank's); one rank: it leaves as it is
+inline void public_section(const Inputs &in, ShardBlock &blk) {
+    const size_t G = in.shard.world;
+    for (size_t q = in.shard.rank; q < 4 && !blk.failed; q += G) {
+        try {
+            check_public(in, blk, q);
+        } catch (const Error &e) {
+            if (G == 1 || e.code != TKMK_ERR_INVALID_ARGUMENT) throw;
+            blk.failed = 1, blk.failed_placement = (uint32_t)q;
+            snprintf(blk.error, sizeof blk.error, "%s", e.what());
         }
     }
-    std::vector<ShardBlock> all(G);
-    check(sh.link->all_gather_host(sh.link->comm, &blk, sizeof blk, all.data()), "tkmk_comm_all_gather_host");
-    const ShardBlock *failed = nullptr;   // the text of the lowest failing placement, as the unsharded walk would meet it, on every rank
+}
+
+// The report from every rank's block (rank order; one block when there is one rank): host work over replicated data alone, so the same
+// on every rank.  A block's input error is thrown — the text of the lowest failing placement, as a walk over all placements would meet it.
+inline bool merge(const Inputs &in, const std::vector<ShardBlock> &all, Report &rep) {
+    const size_t s_max = in.sp->s_max;
+    const EffectivePermutation &ep = *in.perm;
+    const ShardBlock *failed = nullptr;
     for (const ShardBlock &b : all)
         if (b.failed && (!failed || b.failed_placement < failed->failed_placement)) failed = &b;
     if (failed) throw Error(std::string(failed->error, strnlen(failed->error, sizeof failed->error)));
-
-    // ---- the merge: the same on every rank
     rep.arithmetic.placements = in.layout->id.size();
-    rep.copy.entries = in.perm->dst.size();
+    rep.copy.entries = ep.dst.size();
     uint32_t twice = 0;
-    rep.copy.bijection = is_bijection(*in.perm, s_max, &twice);   // over the replicated arrays: no exchange, the same answer everywhere
+    rep.copy.bijection = is_bijection(ep, s_max, &twice);
     rep.copy.twice_row = twice / (uint32_t)s_max, rep.copy.twice_col = twice % (uint32_t)s_max;
     std::vector<ShardBlock::Arithmetic> fa;
     std::vector<ShardBlock::Copy> fc;
@@ -477,7 +425,6 @@ inline bool run_sharded(const Inputs &in, const ShardInputs &sh, Report &rep) {
         rep.arithmetic.first.push_back(ArithmeticFinding{(size_t)fa[k].placement, info.id, info.name, fa[k].first_row, fa[k].bad_rows, fa[k].u, fa[k].v, fa[k].w});
     }
     for (size_t k = 0; k < fc.size() && k < MAX_FINDINGS; k++) {
-        const EffectivePermutation &ep = *in.perm;
         const uint64_t e = fc[k].entry;
         rep.copy.first.push_back(CopyFinding{e, ep.dst.at(e) / (uint32_t)s_max, ep.dst.at(e) % (uint32_t)s_max, ep.x.at(e), ep.y.at(e), fc[k].value, fc[k].source});
     }
@@ -487,6 +434,21 @@ inline bool run_sharded(const Inputs &in, const ShardInputs &sh, Report &rep) {
     rep.copy.ok = rep.copy.bijection && rep.copy.bad_entries == 0;
     rep.pub.ok = rep.pub.bad == 0;
     return conclude(rep);
+}
+
+// The three sections on rank in.shard.rank of G = in.shard.world, then the merge.  G > 1 is collective: every rank calls it, every rank
+// gets the same report and verdict.  Exchanges: one tkmk_comm_all_gather_dev (none when the permutation is empty) and one
+// tkmk_comm_all_gather_host; none at all with G = 1, communicator or not.  A device or transport failure leaves as an exception with the
+// peers possibly waiting: the caller aborts the communicator (ProverContext does).
+inline bool run(const Inputs &in, Report &rep) {
+    ShardBlock blk;
+    std::memset(&blk, 0, sizeof blk);
+    arithmetic_section(in, blk);
+    copy_section(in, blk);
+    public_section(in, blk);
+    std::vector<ShardBlock> all(in.shard.world, blk);
+    if (in.shard.world > 1) check(in.link->all_gather_host(in.link->comm, &blk, sizeof blk, all.data()), "tkmk_comm_all_gather_host");
+    return merge(in, all, rep);
 }
 }  // namespace witness_check
 }  // namespace tkmk

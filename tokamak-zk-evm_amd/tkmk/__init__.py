@@ -854,6 +854,15 @@ def _witness_check_fn(name):
     return fn
 
 
+def _witness_check_copy_call(name, *args):
+    """one of the two copy entries -> (bad_entries, first_bad_entry or None, in_range); code 11 is "some entry out of range", not an error"""
+    bad, first = ctypes.c_uint64(), ctypes.c_uint64()
+    code = _witness_check_fn(name)(*args, ctypes.byref(bad), ctypes.byref(first), None)
+    if code not in (0, 11):
+        raise TkmkError(code, name)
+    return bad.value, (None if first.value == (1 << 64) - 1 else first.value), code == 0
+
+
 def witness_check_r1cs(u, v, w, n_rows, n_cols, stride=None, outs=None):
     """tkmk_witness_check_r1cs over three DeviceBuffers of plain Fr, element (row, col) at row * stride + col: does u . v = w hold in every
     cell of n_rows x n_cols?  -> (bad_count, first_bad_row, total_bad): two uint32 arrays of n_cols entries (failing rows per column; the
@@ -874,12 +883,8 @@ def witness_check_copy(b, rows, cols, stride, dst_idx, src_x, src_y):
     n = arrs[0].size
     assert arrs[1].size == n and arrs[2].size == n
     dev = [DeviceBuffer.from_host(a.view(np.uint8)) if n else None for a in arrs]
-    bad, first = ctypes.c_uint64(), ctypes.c_uint64()
-    code = _witness_check_fn("tkmk_witness_check_copy")(b.ptr if b is not None else None, rows, cols, stride, *[d.ptr if d is not None else None for d in dev],
-                                                         n, ctypes.byref(bad), ctypes.byref(first), None)
-    if code not in (0, 11):
-        raise TkmkError(code, "tkmk_witness_check_copy")
-    return bad.value, (None if first.value == (1 << 64) - 1 else first.value), code == 0
+    return _witness_check_copy_call("tkmk_witness_check_copy", b.ptr if b is not None else None, rows, cols, stride,
+                                    *[d.ptr if d is not None else None for d in dev], n)
 
 
 def witness_check_copy_split(b_local, local_cells, dst_local, sources, n_sources, src_slot):
@@ -896,13 +901,8 @@ def witness_check_copy_split(b_local, local_cells, dst_local, sources, n_sources
         n = arrs[0].size
         assert arrs[1].size == n
         dev = [DeviceBuffer.from_host(a.view(np.uint8)) if n else None for a in arrs]
-    bad, first = ctypes.c_uint64(), ctypes.c_uint64()
     ptr = lambda d: d.ptr if d is not None else None                                               # noqa: E731
-    code = _witness_check_fn("tkmk_witness_check_copy_split")(ptr(b_local), local_cells, ptr(dev[0]), ptr(sources), n_sources, ptr(dev[1]), n,
-                                                               ctypes.byref(bad), ctypes.byref(first), None)
-    if code not in (0, 11):
-        raise TkmkError(code, "tkmk_witness_check_copy_split")
-    return bad.value, (None if first.value == (1 << 64) - 1 else first.value), code == 0
+    return _witness_check_copy_call("tkmk_witness_check_copy_split", ptr(b_local), local_cells, ptr(dev[0]), ptr(sources), n_sources, ptr(dev[1]), n)
 
 
 class ExprInstr(ctypes.Structure):
