@@ -196,7 +196,8 @@ tkmk_error tkmk_prover_verify_batch(tkmk_prover *p, const tkmk_verify_item *item
  * without a device (TKMK_ERR_NO_DEVICE).  report_json_out (optional, tkmk_prover_free_string): {"ok", "reason", "sections": [{"name",
  * "points", "infinity", "noncanonical", "off_curve", "not_in_subgroup", "first_bad"}], "g2", "anchors", "ratio_y", "ratio_x", "seconds":
  * {"upload", "membership", "g2", "msm", "pairings", "total"}, "circuit", "tables", "table_seconds"} — null for a step that was not
- * reached, first_bad null when none; the last three keys are null from this entry. */
+ * reached, first_bad null when none; the last three keys are null from this entry.  The three keys of the locate pass follow
+ * (tkmk_crs_audit_files_ex below; from this entry "located": null, "locate_products": 0). */
 tkmk_error tkmk_crs_audit_files(const char *subcircuit_library_dir, const char *crs_dir, int *ok, char **report_json_out);
 /* The same contract, plus the table checks against the circuit: needs <lib>/subcircuitInfo.json and <lib>/r1cs/subcircuit{id}.r1cs as well
  * (a missing or malformed file is an error return, not a verdict).  After everything above has passed — the table checks rest on
@@ -212,10 +213,33 @@ tkmk_error tkmk_crs_audit_files(const char *subcircuit_library_dir, const char *
  * The root of unity the Lagrange bases are taken over is identified from the CRS first, as tkmk_prover_open does (a CRS made under
  * generator 7 audits as one made under 5; adopting it is process-wide).  Together this fixes all seven G1 tables and the single points,
  * and sigma_2 except that gamma, delta, eta are tied to the tables only, not to each other.  NOT covered: sigma_preprocess.rkyv, the
- * sharded open, BN254.  Which record of a failed table is wrong is not located.  The seed caveat above holds unchanged.
+ * sharded open, BN254.  Which record of a failed table is wrong is what TKMK_CRS_AUDIT_LOCATE (below) finds.  The seed caveat above holds unchanged.
  * Report: "circuit" true / false (null when an earlier step failed), "tables": [{"name", "points", "ok"}] for gamma, eta, delta,
  * delta_small, alpha_chain, singles (an empty table is vacuously ok with 0 points), "table_seconds": {"library", "grids", "msm", "pairings"}. */
 tkmk_error tkmk_crs_audit_circuit_files(const char *subcircuit_library_dir, const char *crs_dir, int *ok, char **report_json_out);
+/* The audit by flags: 0 is tkmk_crs_audit_files, TKMK_CRS_AUDIT_CIRCUIT is tkmk_crs_audit_circuit_files (both are calls of this entry), and
+ * TKMK_CRS_AUDIT_LOCATE adds the locate pass to either: a STRUCTURAL check that fails (a membership failure names its record already) goes
+ * on to name the record, or says that the failure is not a record's.  Every equation of the audit is linear in its weights, so a failing
+ * check splits into two half-checks over the same scalars — nothing new is drawn — and the first bad record is about log2(N) evaluations
+ * of an equation that exists already away; one more evaluation with that record's terms set aside decides `more`.
+ *   xy_powers (ratio_y / ratio_x false; without TKMK_CRS_AUDIT_CIRCUIT this is all the pass covers)   per failed direction first
+ *       e(sigma_1.y, H) = e(G, sigma_2.y) (resp. x): if that fails, sigma_2 is at fault and no record is searched for.  Else the rectangle
+ *       of relations is bisected, rows then columns, over views of the uploaded table; the record named is the one that the first
+ *       failing relations of both directions touch, else the relation is reported with "index": null.
+ *   gamma, eta, delta   the table's equation restricted to a range of rows (eta / delta: then to a range of placement columns of the row
+ *       found); the last step is the equation of one record, an exact statement.  A step costs one evaluation of the table's equation.
+ *   delta_small, alpha_chain, singles   the records one at a time.
+ * A search runs only where the check's own prerequisites held.  With the flag clear the call is the entry without it: the same launches,
+ * report text and reason; with it set and an honest CRS nothing extra runs.  tkmk_prover_open never locates (TKMK_PROVER_CHECK_CRS): run
+ * this, or bin/crs-check --locate, after a refusal.  Not on a sharded prover, not for BN254; one record per check (the first in index order).
+ * Report: three keys after all of the above — "located": null without the flag, [] when nothing was located, else in check order
+ * [{"check": "ratio_y" | "ratio_x" | "gamma" | "eta" | "delta" | "delta_small" | "alpha_chain" | "singles", "section": the payload section,
+ * "index", "row", "col" (null where they do not apply), "more": the section still fails without the record, "what": one sentence}];
+ * "locate_products": pairing products spent locating; "locate_seconds".  "reason" keeps its text, the first finding's "what" appended.
+ * TKMK_ERR_INVALID_ARGUMENT for an unknown flag bit. */
+#define TKMK_CRS_AUDIT_CIRCUIT 1
+#define TKMK_CRS_AUDIT_LOCATE 2
+tkmk_error tkmk_crs_audit_files_ex(const char *subcircuit_library_dir, const char *crs_dir, uint32_t flags, int *ok, char **report_json_out);
 
 /* ---- The witness check (host/tkmk_witness_check.hpp; needs a device and NO reference string) ----
  * Reads the library (<lib>/setupParams.json, subcircuitInfo.json, r1cs/) and the three per-proof documents of synthesizer_dir, puts the

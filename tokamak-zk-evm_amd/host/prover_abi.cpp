@@ -195,23 +195,28 @@ TKP_API tkmk_error tkmk_verify_files(const char *subcircuit_library_dir, const c
 }
 
 // the CRS audit (host/tkmk_crs_audit.hpp): device work on the default stream, so it takes the unsharded contexts' turn
-static tkmk_error crs_audit_entry(const char *entry, const char *subcircuit_library_dir, const char *crs_dir, bool circuit, int *ok, char **report_json_out) {
+static tkmk_error crs_audit_entry(const char *entry, const char *subcircuit_library_dir, const char *crs_dir, uint32_t flags, int *ok, char **report_json_out) {
     if (!subcircuit_library_dir || !crs_dir || !ok) return TKMK_ERR_INVALID_POINTER;
     return verdict_entry(ok, report_json_out, [&] {
+        if (flags & ~(uint32_t)(TKMK_CRS_AUDIT_CIRCUIT | TKMK_CRS_AUDIT_LOCATE)) throw Error(TKMK_ERR_INVALID_ARGUMENT, std::string(entry) + ": unknown flag bits");
         int ndev = 0;
         if (tkmk_device_count(&ndev) != TKMK_SUCCESS || ndev < 1) throw Error(TKMK_ERR_NO_DEVICE, std::string(entry) + ": no HIP device (the MI355X backend has no CPU fallback)");
         DefaultStreamTurn turn(false);
         crs_audit::Report rep;
-        const bool verdict = crs_audit::audit_files(subcircuit_library_dir, crs_dir, rep, nullptr, circuit);
+        const bool verdict = crs_audit::audit_files(subcircuit_library_dir, crs_dir, rep, nullptr, (flags & TKMK_CRS_AUDIT_CIRCUIT) != 0, (flags & TKMK_CRS_AUDIT_LOCATE) != 0);
         hand_over(verdict, rep, ok, report_json_out);
     });
 }
-TKP_API tkmk_error tkmk_crs_audit_files(const char *subcircuit_library_dir, const char *crs_dir, int *ok, char **report_json_out) {
-    return crs_audit_entry("tkmk_crs_audit_files", subcircuit_library_dir, crs_dir, false, ok, report_json_out);
+// flags: TKMK_CRS_AUDIT_CIRCUIT = plus the gamma / eta / delta tables against the circuit of the library (audit_tables), TKMK_CRS_AUDIT_LOCATE =
+// a failed structural check goes on to name the record
+TKP_API tkmk_error tkmk_crs_audit_files_ex(const char *subcircuit_library_dir, const char *crs_dir, uint32_t flags, int *ok, char **report_json_out) {
+    return crs_audit_entry("tkmk_crs_audit_files_ex", subcircuit_library_dir, crs_dir, flags, ok, report_json_out);
 }
-// ... plus the gamma / eta / delta tables against the circuit of the library (audit_tables)
+TKP_API tkmk_error tkmk_crs_audit_files(const char *subcircuit_library_dir, const char *crs_dir, int *ok, char **report_json_out) {
+    return crs_audit_entry("tkmk_crs_audit_files", subcircuit_library_dir, crs_dir, 0, ok, report_json_out);
+}
 TKP_API tkmk_error tkmk_crs_audit_circuit_files(const char *subcircuit_library_dir, const char *crs_dir, int *ok, char **report_json_out) {
-    return crs_audit_entry("tkmk_crs_audit_circuit_files", subcircuit_library_dir, crs_dir, true, ok, report_json_out);
+    return crs_audit_entry("tkmk_crs_audit_circuit_files", subcircuit_library_dir, crs_dir, TKMK_CRS_AUDIT_CIRCUIT, ok, report_json_out);
 }
 
 // the witness check (host/tkmk_witness_check.hpp; ProverContext::check_witness): device work on the default stream, like a proof

@@ -21,7 +21,7 @@ SYMBOLS = ["tkmk_prover_open", "tkmk_prover_open_sharded", "tkmk_prover_world_si
            "tkmk_prover_crs_source", "tkmk_prover_root_generator",
            "tkmk_pairing_product_is_one", "tkmk_verify_files", "tkmk_prover_verify",      # the verifier: bound in tkmk/verify.py
            "tkmk_verify_batch_files", "tkmk_prover_verify_batch",                        # batch verification: tkmk.verify.verify_batch[_with]
-           "tkmk_crs_audit_files", "tkmk_crs_audit_circuit_files",                                                   # the CRS audit: tkmk.verify.crs_audit
+           "tkmk_crs_audit_files", "tkmk_crs_audit_circuit_files", "tkmk_crs_audit_files_ex",                                                 # the CRS audit: tkmk.verify.crs_audit
            "tkmk_witness_check_files", "tkmk_prover_check_witness", "tkmk_prover_check_witness_sharded"]                                                  # the witness check: tkmk.verify.witness_check
 
 

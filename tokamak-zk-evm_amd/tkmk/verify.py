@@ -19,6 +19,7 @@ def _lib(testing=False):
         l.tkmk_prover_verify.argtypes = [ctypes.c_void_p] + [ctypes.c_char_p] * 3 + [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p)]
         l.tkmk_crs_audit_files.argtypes = [ctypes.c_char_p] * 2 + [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p)]
         l.tkmk_crs_audit_circuit_files.argtypes = l.tkmk_crs_audit_files.argtypes
+        l.tkmk_crs_audit_files_ex.argtypes = [ctypes.c_char_p] * 2 + [ctypes.c_uint32, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p)]
         l.tkmk_witness_check_files.argtypes = [ctypes.c_char_p] * 2 + [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p)]
         l.tkmk_prover_check_witness.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_void_p)]
         l.tkmk_prover_check_witness_sharded.argtypes = l.tkmk_prover_check_witness.argtypes
@@ -133,7 +134,10 @@ def verify_batch_with(prover, items, route="host"):
     return [bool(v) for v in each[:len(items)]], rep
 
 
-def crs_audit(subcircuit_library_dir, crs_dir, testing=False, circuit=False):
+AUDIT_CIRCUIT, AUDIT_LOCATE = 1, 2         # TKMK_CRS_AUDIT_* of include/tkmk_prover.h
+
+
+def crs_audit(subcircuit_library_dir, crs_dir, testing=False, circuit=False, locate=False):
     """-> (ok, report): tkmk_crs_audit_files — is the reference string <crs_dir>/combined_sigma.{tkcrs, rkyv} well formed for the circuit of
     <subcircuit_library_dir>: membership of every G1 record on the device (tkmk_g1_check) and of the ten G2 points on the host, the anchors,
     and the power structure of xy_powers by four MSMs and two pairing products.  report = {"ok", "reason", "sections": [{"name", "points",
@@ -142,11 +146,21 @@ def crs_audit(subcircuit_library_dir, crs_dir, testing=False, circuit=False):
     circuit=True: tkmk_crs_audit_circuit_files — after all of that, the gamma / eta / delta tables, the small delta tables and the single
     points against the circuit (<lib>/subcircuitInfo.json, <lib>/r1cs/) and sigma_2; the report's "circuit" is then the verdict of those
     checks, "tables" = [{"name", "points", "ok"}] for gamma, eta, delta, delta_small, alpha_chain, singles and "table_seconds" their
-    times (all three are None without it)."""
+    times (all three are None without it).
+    locate=True: tkmk_crs_audit_files_ex with TKMK_CRS_AUDIT_LOCATE — a structural check that fails goes on to name the record: the
+    report's "located" is then a list, in check order, of {"check", "section", "index", "row", "col", "more", "what"} (index None where the
+    failure is not one record's, e.g. a wrong sigma_2.y; [] when nothing was located), "locate_products" the pairing products that took
+    and "locate_seconds" their time; "reason" has the first finding's "what" appended.  Without circuit=True it covers xy_powers only.
+    Without locate the call, its launches and its report text are what they were ("located" is None)."""
     l = _lib(testing)
     ok, doc = ctypes.c_int(-1), ctypes.c_void_p()
-    name = "tkmk_crs_audit_circuit_files" if circuit else "tkmk_crs_audit_files"
-    code = getattr(l, name)(os.fsencode(subcircuit_library_dir), os.fsencode(crs_dir), ctypes.byref(ok), ctypes.byref(doc))
+    if locate:
+        name = "tkmk_crs_audit_files_ex"
+        code = l.tkmk_crs_audit_files_ex(os.fsencode(subcircuit_library_dir), os.fsencode(crs_dir), AUDIT_LOCATE | (AUDIT_CIRCUIT if circuit else 0),
+                                         ctypes.byref(ok), ctypes.byref(doc))
+    else:
+        name = "tkmk_crs_audit_circuit_files" if circuit else "tkmk_crs_audit_files"
+        code = getattr(l, name)(os.fsencode(subcircuit_library_dir), os.fsencode(crs_dir), ctypes.byref(ok), ctypes.byref(doc))
     if code != 0:
         raise service.ProverError(code, name, testing)
     return ok.value == 1, _take_report(l, doc)
